@@ -1,6 +1,11 @@
 """Benchmark of the hot path: utterances/sec of the full audio-visual CTC training step (fwd + bwd + Adam).
 
   python bench.py --gpus N --steps K --warmup W            (N > 1: one rank per GPU over RCCL)
+  python bench.py ... --full                               (also: other variant, roofline + attention legs, CPU baseline)
+  python bench.py ... --dump-outputs DIR                   (the last timed step's outputs as DIR/<name>.npy)
+
+A plain run times the headline variant only: set-up, W warm-up steps, K timed steps, the optional dump, one JSON line.  Everything else
+the line can carry (``other_variant``, ``roofline``, ``attention``, ``cpu_baseline``) is measured in legs of their own under ``--full``.
 
 Workload = the configuration BASELINE.json's metric is quoted on: batch 64 per GPU x 4 s clips (64 000 samples @16 kHz + 100 lip
 frames 96x96 per speaker), wav2vec2-large architecture, random-init weights, synthetic data, bf16 MFMA compute with fp32 master
@@ -82,6 +87,33 @@ def cpu_baseline(cfg, seconds):
             "sample": f"B={B} x {seconds:g} s clips, {n} fp32 steps after 1 warm-up, two audio passes as the reference runs it"}
 
 
+DUMP_MAX_ELEMS = 1 << 20          # per array; a larger one is written as a fixed, seeded sample of this many of its elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, trainable):
+    """--dump-outputs: what the timed path handed back in its last step (train_step's dict) and the trainable parameters its Adam step
+    left behind (flattened in module order), one float32 ``<name>.npy`` each.  An array of more than DUMP_MAX_ELEMS elements is written as
+    the sample at the same sorted, seeded positions of its flattened values whenever its size is the same, so that two builds compare
+    element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(out)
+    arrays["trainable_params"] = torch.cat([p.detach().reshape(-1).float() for p in trainable])
+    total = 0
+    for name, x in sorted(arrays.items()):
+        x = torch.as_tensor(x).detach()
+        n = x.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        a = x.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 HF_REGULARIZERS = dict(hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, feat_proj_dropout=0.0, layerdrop=0.1,
                        mask_time_prob=0.05, mask_time_length=10, mask_time_min_masks=2)
 NO_REGULARIZERS = dict(hidden_dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, feat_proj_dropout=0.0, layerdrop=0.0,
@@ -153,7 +185,7 @@ def attention_report(records, steps):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -165,10 +197,14 @@ def main():
                     help="headline variant.  as_executed: two audio passes with HF-default dropout / LayerDrop / SpecAugment, what the reference's "
                          "train_epoch runs (model/trainer.py:94-95); deterministic: every regulariser 0 (the parity configuration), where the "
                          "two passes are bit-identical and the encoder runs once")
-    ap.add_argument("--single-variant", action="store_true", help="time only the headline variant")
+    ap.add_argument("--full", action="store_true", help="also the legs beside the headline figure: the other variant, the roofline / attention probe "
+                                                        "leg and the CPU baseline (each can be left out with the three options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the outputs of the last one (train_step's dict and the "
+                                                          "trainable parameters after its Adam step) as DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--single-variant", action="store_true", help="with --full: time only the headline variant")
     ap.add_argument("--lambda", dest="lambda_", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: no roofline / attention probe leg")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo + --same-device rehearses N>1 on a 1-GPU box")
     ap.add_argument("--same-device", action="store_true")
     ap.add_argument("--force-dp", action="store_true", help="build the process group and the gradient reducer even with one rank (RCCL path rehearsal)")
@@ -178,7 +214,14 @@ def main():
     ap.add_argument("--h2d", action="store_true", help="also time the headline variant with the host->device leg of the reference's step (model/trainer.py:66-75) "
                                                        "INSIDE the timed region: batches in pinned host memory, copied one step ahead on a prefetch stream "
                                                        "(double buffer).  `value` stays the HBM-resident number; the line gains an `h2d` object")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.single_variant = args.no_probe = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))        # nothing above has initialised the GPU
@@ -239,8 +282,8 @@ def main():
 
     # Every leg (headline, other variant, roofline probe) starts from the SAME state: initial weights, BatchNorm running statistics, fresh
     # optimizer / scaler state.  No leg runs on the weights another leg left behind.
-    state_tensors = [p for m in (t.audio_encoder, t.fusion_module, t.decoder1) for p in m.parameters() if p.requires_grad]
-    state_tensors += [b for b in t.visual_encoder.buffers()]
+    trainable = [p for m in (t.audio_encoder, t.fusion_module, t.decoder1) for p in m.parameters() if p.requires_grad]
+    state_tensors = trainable + [b for b in t.visual_encoder.buffers()]
     snap = [x.detach().clone() for x in state_tensors]
 
     def restore():
@@ -260,7 +303,7 @@ def main():
 
     pinned = None
 
-    def timed(v, h2d=False):
+    def timed(v, h2d=False, keep=False):
         nonlocal pinned
         restore()
         passes = set_variant(v)
@@ -333,7 +376,7 @@ def main():
             ok = bool(fl_.item() > 0.5)
         return dict(dt=dt, passes=passes, loss=loss_v, layers=lay, valid=ok, variant=v, dp=dpi,
                     scale=(t.scaler.get_scale(), t.scaler.steps_taken()) if args.loss_scaling else None,
-                    h2d_bytes=(pf.bytes_last if pf is not None else None))
+                    h2d_bytes=(pf.bytes_last if pf is not None else None), out=out if keep else None)
 
     def diverged(leg):
         if rank == 0:
@@ -348,9 +391,12 @@ def main():
         raise SystemExit(3)
 
     other = "deterministic" if args.variant == "as_executed" else "as_executed"
-    head_leg = timed(args.variant)
+    head_leg = timed(args.variant, keep=bool(args.dump_outputs))
     if not head_leg["valid"]:
         diverged(head_leg)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head_leg["out"], trainable)      # before any other leg re-runs the step on these buffers
+    head_leg["out"] = None
     second = None if args.single_variant else timed(other)
     if second is not None and not second["valid"]:
         diverged(second)

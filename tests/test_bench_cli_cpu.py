@@ -62,3 +62,39 @@ def test_flop_accounting_counts_executed_layers():
     assert abs((full - got) - ((lin + att) + (lin + att) + (2 * lin + 2 * att))) < 1.0
     # per-step averages need not be integers (LayerDrop over 30 timed steps)
     assert b.flops_per_utt(cfg, 64000, 100, 2, (43.0, 25.13, 7.13)) < full
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small arrays are written whole in float32, a large one as a seeded sample at the same positions from run to run,
+    the trainable parameters flattened in order; the whole dump stays within 64 MB."""
+    import numpy as np
+    import torch
+    b = _load_bench()
+    big = torch.arange(3 * b.DUMP_MAX_ELEMS, dtype=torch.float64).reshape(3, -1)
+    out = {"total": torch.tensor(1.5), "lengths": torch.tensor([3, 4]), "big": big.to(torch.bfloat16)}
+    params = [torch.ones(2, 3), torch.zeros(5)]
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), out, params)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"total", "lengths", "big", "trainable_params"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert float(got["total"]) == 1.5 and got["lengths"].tolist() == [3.0, 4.0]
+    assert got["trainable_params"].tolist() == [1.0] * 6 + [0.0] * 5
+    s = got["big"]
+    assert s.shape == (b.DUMP_MAX_ELEMS,) and np.all(np.diff(s) >= 0)            # sorted positions of an increasing array
+    assert np.array_equal(s, big.reshape(-1).to(torch.bfloat16).float().numpy()[np.sort(np.random.default_rng(0).choice(big.numel(), b.DUMP_MAX_ELEMS, replace=False))])
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """Without --full a run times the headline variant only (no other variant, probe leg or CPU baseline); --full brings them back, and
+    the three options that leave one of them out still work under it."""
+    b = _load_bench()
+    a = b.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.single_variant and a.no_probe and a.no_cpu_baseline
+    a = b.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and not (a.single_variant or a.no_probe or a.no_cpu_baseline)
+    a = b.parse_args(["--full", "--no-cpu-baseline"])
+    assert a.no_cpu_baseline and not (a.single_variant or a.no_probe)

@@ -152,7 +152,7 @@ def test_bench_starts_its_own_ranks():
     import subprocess
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "2",
-                        "--warmup", "1", "--batch", "4", "--seconds", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+                        "--warmup", "1", "--batch", "4", "--seconds", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
                        env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -77,6 +77,26 @@ def test_bench_h2d_leg_reports_the_copy_inside_the_timed_region():
     assert abs(h["final_loss"] - d["config"]["final_loss"]) < 5e-3 and h["exposed_ms"] == pytest.approx(h["ms_per_step"] - d["ms_per_step"], abs=2e-3)
 
 
+def test_bench_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) carries the headline figure only, and --dump-outputs writes the last timed step's outputs as float32 .npy
+    files: the dumped total loss is the line's final_loss."""
+    import numpy as np
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4", "--seconds", "1", "--steps", "3", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["valid"] is True
+    assert not {"other_variant", "cpu_baseline", "attention"} & set(d) and d["roofline"] is None
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"total", "loss1", "loss2", "log_probs1", "log_probs2", "trainable_params"} <= set(files)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert abs(float(files["total"]) - d["config"]["final_loss"]) < 1e-4
+
+
 def test_bench_force_dp_single_rank_rccl_leg():
     """One rank, real RCCL process group: every bucket after the first step is all-reduced IN PLACE (no packing copy), the exposed
     all-reduce time is reported, and the line carries the observed world size and the all-reduce checksum."""
