@@ -278,6 +278,22 @@ int av_loss_combine(const float* nll, const float* w, const float* c1, const flo
  * [B][T][V], lengths optional int64 [B] (frames to decode); out_ids int32 [B][T] = collapsed ids padded with -1, out_len int32 [B] */
 int av_ctc_greedy(const float* log_probs, const long long* lengths, int* out_ids, int* out_len, int B, int T, int V, int blank,
                   void* stream);
+/* CTC loss on the device, opt-in replacement of nn.CTCLoss(blank, zero_infinity=True) (model/trainer.py:25,116-117): the semantics of
+ * torch.nn.functional.ctc_loss(..., reduction="none") with padded 2-D targets.  log_probs fp32, element [b][t][v] at
+ * b * stride_b + t * stride_t + v (element strides: [B][T][V] and the [T][B][V] view are both taken without a copy); targets int64
+ * [B][target_ld]; input_lengths / target_lengths int64 [B].  Labels and lengths are read from DEVICE memory (no host copy, no
+ * synchronisation); T_b is clamped to [0, T], L_b to [0, Lmax = (S_max - 1) / 2], an item with a label outside [0, V) is infeasible.
+ * av_ctc_loss_fwd: nll fp32 [B] (+inf for an infeasible item, 0 with zero_infinity); log_alpha / log_beta = workspaces fp32
+ * [B][T][S_max] for the gradient (log_beta NULL: loss only, log_alpha may then be NULL too).
+ * av_ctc_loss_bwd: grad fp32 [B][T][V] contiguous = grad_nll[b] * (exp(log_probs) - occupancy) for t < T_b (torch's form: rows sum to
+ * zero), exactly 0 for t >= T_b and for every frame of an infeasible item; nll / log_alpha / log_beta as written by the forward.
+ * Deterministic: no floating-point atomics (bit-identical results for identical inputs). */
+int av_ctc_loss_fwd(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
+                    const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
+                    int zero_infinity, float* nll, float* log_alpha, float* log_beta, void* stream);
+int av_ctc_loss_bwd(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
+                    const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
+                    const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll, float* grad, void* stream);
 /* device side of the input pipeline (dataset/multi_speaker_dataset.py:13-59; decoding wav / npy files stays on the host):
  * av_lip_gray_resize: src [T][Hs][Ws][C] (uint8 if src_is_u8 else fp32) -> dst fp32 [T][Hd][Wd] = bilinear(mean over C) / divisor
  *   (:49-58: .astype(float32).mean(-1), cv2.resize INTER_LINEAR law, / 255), float32 operation order of the reference;

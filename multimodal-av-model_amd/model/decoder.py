@@ -1,5 +1,6 @@
 """CTCDecoder on the HIP kernels (model/decoder.py:6-35): Linear(input_dim -> vocab) + log_softmax as one MFMA
-GEMM + a wavefront-per-row log-softmax.  nn.CTCLoss itself stays on PyTorch-ROCm (BASELINE north_star).
+GEMM + a wavefront-per-row log-softmax.  nn.CTCLoss itself stays on PyTorch-ROCm by default (BASELINE north_star);
+``native_ctc=True`` (or AVAMD_NATIVE_CTC=1) selects the device CTC kernels of ops.ctc_loss instead.
 """
 from __future__ import annotations
 
@@ -49,10 +50,14 @@ class _HeadFn(torch.autograd.Function):
 
 
 class CTCDecoder(nn.Module):
-    def __init__(self, input_dim, vocab_size, blank_id=0):
+    def __init__(self, input_dim, vocab_size, blank_id=0, native_ctc=None):
         super().__init__()
         self.net = nn.Sequential(nn.Linear(input_dim, vocab_size))     # parameter container: keys net.0.{weight,bias}
         self.ctc_loss = nn.CTCLoss(blank=blank_id, zero_infinity=True)
+        self.blank_id = blank_id
+        # None: the environment variable AVAMD_NATIVE_CTC (default "0"), read here.  On: forward(target=...) computes the loss with
+        # ops.ctc_loss (lengths stay on the device, no synchronisation) instead of nn.CTCLoss
+        self.native_ctc = ops.native_ctc_default() if native_ctc is None else bool(native_ctc)
         self._cache = ParamCache()
         self.grad_arena = None          # parallel.dp.GradArena shared with the fusion module (the trainer's head gradient bucket)
         self._wpad = None               # bf16 weight with zero rows up to a multiple of 64 (see forward)
@@ -82,5 +87,8 @@ class CTCDecoder(nn.Module):
                 wt = self._cache.get("w", [lin.weight], dtype, lambda: ops.cast(lin.weight.data.contiguous(), dtype), flat=True)
         log_probs = _HeadFn.apply(x, lin.weight, lin.bias, wt, self.grad_arena, wpad)
         if target is not None:
+            if self.native_ctc:
+                return ops.ctc_loss(log_probs, target, input_lengths, target_lengths, blank=self.blank_id, reduction="mean",
+                                    zero_infinity=True, batch_first=True)
             return self.ctc_loss(log_probs.transpose(0, 1), target, input_lengths, target_lengths)
         return log_probs

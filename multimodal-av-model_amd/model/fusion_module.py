@@ -259,7 +259,10 @@ class CrossAttentionFusion(nn.Module):
     # another process that also runs persistent kernels) gives up after a bounded spin and raises counters[2]; its results are
     # invalid.  The trainer stages an asynchronous copy of the pending words into pinned memory right before the step's one
     # synchronising call (F.ctc_loss) and looks at them right after it, so a timeout is reported in the step it happened in
-    # (forward launches) or in the next one (backward launches) without adding a synchronisation.
+    # (forward launches) or in the next one (backward launches) without adding a synchronisation.  With the device CTC loss
+    # (MultimodalTrainer(native_ctc=True)) the step has no synchronising call: the copy is staged at the same place, is usually not
+    # complete right after it, and is then evaluated at the start of the next forward_losses (finish_flag_check(wait=True)), at the
+    # end of train_epoch and in evaluate() (drain_flag_check) - late by at most one step, never dropped.
     def stage_flag_check(self):
         if not self._lstm_flags or self._flag_evt is not None:
             return
@@ -272,14 +275,27 @@ class CrossAttentionFusion(nn.Module):
         self._flag_n = n
         del self._lstm_flags[:n]
 
-    def finish_flag_check(self):
-        if self._flag_evt is None or not self._flag_evt.query():
+    def finish_flag_check(self, wait: bool = False):
+        """Look at the staged words if their copy has completed; otherwise leave the check pending (it is never dropped: the next call
+        looks again).  ``wait``: block on the copy's event instead - for a check staged in an EARLIER step (the device CTC path has no
+        synchronising call behind which the words become visible), whose event has normally long completed: no stream is drained."""
+        if self._flag_evt is None:
             return
+        if not self._flag_evt.query():
+            if not wait:
+                return
+            self._flag_evt.synchronize()
         bad = int(self._flag_host[: self._flag_n].max()) != 0
         self._flag_evt = None
         if bad:
             raise RuntimeError("persistent LSTM kernel: inter-workgroup wait timed out (the step that launched it is invalid); "
                                "AVAMD_LSTM_PERSISTENT=0 selects the per-step kernels (e.g. on a GPU shared with other processes)")
+
+    def drain_flag_check(self):
+        """Blocking form for the end of an epoch / of evaluate(): every pending word, staged or not, is evaluated before returning."""
+        while self._flag_evt is not None or self._lstm_flags:
+            self.stage_flag_check()
+            self.finish_flag_check(wait=True)
 
     def _grad_out(self, name: str, shape, device, vec: bool = False):
         """View of the flat gradient bucket for this gradient, or None (no bucket / layout not known yet / already written this step).

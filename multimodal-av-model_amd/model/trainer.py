@@ -73,7 +73,7 @@ class _CombineFn(torch.autograd.Function):
 class MultimodalTrainer:
     def __init__(self, visual_encoder, audio_encoder, fusion_module, decoder1, tokenizer, learning_rate=1e-4, device="cuda",
                  lambda_=0.1, audio_passes: Optional[int] = None, reducer: Optional[GradBucketReducer] = None, pair_batched: bool = True,
-                 visual_side_stream: bool = True, loss_scaling: bool = False):
+                 visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -88,7 +88,11 @@ class MultimodalTrainer:
         self.pair_batched = pair_batched
         self.visual_side_stream = visual_side_stream
         self._vstream = None
-        self.ctc_loss = nn.CTCLoss(blank=tokenizer.blank_id, zero_infinity=True)       # stays on PyTorch-ROCm
+        self.ctc_loss = nn.CTCLoss(blank=tokenizer.blank_id, zero_infinity=True)       # stays on PyTorch-ROCm (the default)
+        # opt-in: the CTC loss of both branches of forward_losses (and so of evaluate()) on the device kernels of ops.ctc_loss.  None reads
+        # AVAMD_NATIVE_CTC (default "0") here.  Lengths and targets stay on the device: the step then holds no synchronising call and
+        # ignores the host copies ``_ctc_input_lengths`` / ``_ctc_target_lengths`` of host_metadata()
+        self.native_ctc = ops.native_ctc_default() if native_ctc is None else bool(native_ctc)
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.optimizer = AvAdam([
@@ -190,7 +194,13 @@ class MultimodalTrainer:
                 "_audio_valid1": (cpu_batch["mask1"] != 3).sum(1).tolist(), "_audio_valid2": (cpu_batch["mask2"] != 3).sum(1).tolist()}
 
     def forward_losses(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """model/trainer.py:66-119 for one batch; everything stays on the device."""
+        """model/trainer.py:66-119 for one batch; everything stays on the device.
+
+        With ``native_ctc`` nothing in here synchronises, so the BiLSTM timeout words staged by a step are normally evaluated at the
+        start of the NEXT call (or at the end of train_epoch / evaluate()): the RuntimeError of a timed-out persistent LSTM launch then
+        names the previous step, not the one that is being enqueued."""
+        if self.native_ctc:
+            self.fusion_module.finish_flag_check(wait=True)        # staged one step ago: its event has completed unless the host runs far ahead
         d = self._to_dev(batch)
         use_side = self.visual_side_stream and d["audio"].is_cuda
         if use_side:
@@ -294,8 +304,13 @@ class MultimodalTrainer:
             il_h, tl_h = batch.get("_ctc_input_lengths"), batch.get("_ctc_target_lengths")     # host copies: no device sync in ctc_loss
             w_ctc = (0.5 / B) / tl.clamp_min(1).to(torch.float32)        # weights of the per-speaker means (before the CTC call: off the sync)
             self.fusion_module.stage_flag_check()                  # BiLSTM timeout words -> pinned memory, visible after ctc_loss's own sync
-            nll = F.ctc_loss(lp12.transpose(0, 1), tg, il12 if il_h is None else il_h, tl if tl_h is None else tl_h,
-                             blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True)
+            if self.native_ctc:
+                # device CTC: lengths and targets are read from device memory, nothing blocks (the staged words are looked at below if
+                # their copy happens to be complete, otherwise by the next forward_losses / train_epoch / evaluate())
+                nll = ops.ctc_loss(lp12, tg, il12, tl, blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True, batch_first=True)
+            else:
+                nll = F.ctc_loss(lp12.transpose(0, 1), tg, il12 if il_h is None else il_h, tl if tl_h is None else tl_h,
+                                 blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True)
             self.fusion_module.finish_flag_check()                 # raises if a persistent BiLSTM launch timed out (event query, no sync)
             if nll.is_cuda and nll.dtype == torch.float32 and _FUSED_LOSS:
                 total, l1, l2 = _CombineFn.apply(nll, w_ctc, c1, c2, float(self.lambda_))    # one kernel forward, one backward
@@ -305,8 +320,15 @@ class MultimodalTrainer:
                 total = None
         else:
             total = None
-            l1 = self.ctc_loss(lp1.transpose(0, 1), d["text1"], il1, d["text1_lengths"])
-            l2 = self.ctc_loss(lp2.transpose(0, 1), d["text2"], il2, d["text2_lengths"])
+            if self.native_ctc:
+                kw = dict(blank=self.tokenizer.blank_id, reduction="mean", zero_infinity=True, batch_first=True)
+                self.fusion_module.stage_flag_check()
+                l1 = ops.ctc_loss(lp1, d["text1"], il1, d["text1_lengths"], **kw)
+                l2 = ops.ctc_loss(lp2, d["text2"], il2, d["text2_lengths"], **kw)
+                self.fusion_module.finish_flag_check()
+            else:
+                l1 = self.ctc_loss(lp1.transpose(0, 1), d["text1"], il1, d["text1_lengths"])
+                l2 = self.ctc_loss(lp2.transpose(0, 1), d["text2"], il2, d["text2_lengths"])
         if total is None:
             total = (l1 + l2) / 2 + self.lambda_ * (c1 + c2) / 2
         out.update(visual_feat1=vf1, visual_feat2=vf2, audio_last=a1, audio_mid=mid1, fused1=f1, fused2=f2, input_lengths1=il1,
@@ -376,6 +398,8 @@ class MultimodalTrainer:
                     # data parallel: a rank that skips a batch no longer issues the collectives its peers are waiting in
                     raise
                 continue
+        if self.native_ctc:
+            self.fusion_module.drain_flag_check()                  # the last step's timeout words: nothing stays pending past the epoch
         return total_loss / max(1, len(dataloader))
 
     def ctc_decode(self, pred_ids):
@@ -405,6 +429,8 @@ class MultimodalTrainer:
                     for i, seq in enumerate(ids):
                         hyps.append(fast_decode(seq, self.tokenizer))
                         refs.append(self.tokenizer.decode(txt[i][: int(tl[i])].tolist()))
+            if self.native_ctc:
+                self.fusion_module.drain_flag_check()
         finally:
             self.lambda_ = lam
         wer1, wer2 = word_error_rate(refs1, hyps1), word_error_rate(refs2, hyps2)

@@ -545,3 +545,95 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, do: Tensor, dq: Tensor, dk: T
          sB=D, oB=k.stride(0), sC=D, oC=dq.stride(0), **bh)
     gemm(dS, q, dk, M=Tk, N=D, K=Tq, lda=ld, ldb=q.stride(1), ldc=dk.stride(1), a_mode=L.A_TRANS, b_mode=L.B_KN,
          sA=Tq * ld, oA=H * Tq * ld, sB=D, oB=q.stride(0), sC=D, oC=dk.stride(0), **bh)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# CTC loss on the device (csrc/ctc_loss.hip): opt-in replacement of nn.CTCLoss (model/trainer.py:25,116-117).  Lengths and targets stay
+# on the device, nothing in the call synchronises.
+# ---------------------------------------------------------------------------------------------------------------
+def native_ctc_default() -> bool:
+    """The environment switch AVAMD_NATIVE_CTC (default "0": nn.CTCLoss on PyTorch-ROCm, as BASELINE north_star prescribes), read when a
+    CTCDecoder / MultimodalTrainer is constructed with ``native_ctc=None``."""
+    return os.environ.get("AVAMD_NATIVE_CTC", "0") != "0"
+
+
+def _ctc_lengths(t, name: str, B: int, device) -> Tensor:
+    if not isinstance(t, Tensor):
+        t = torch.as_tensor(t, dtype=torch.long)
+    if t.dim() != 1 or t.numel() != B:
+        raise ValueError(f"ctc_loss: {name} must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError(f"ctc_loss: {name} must be an integer tensor, got {t.dtype}")
+    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()        # a host tensor is copied without blocking
+
+
+class _CtcLossFn(torch.autograd.Function):
+    """nll [B] = av_ctc_loss_fwd; d nll / d log_probs = av_ctc_loss_bwd (torch's form: grad_nll (exp(lp) - occupancy))."""
+
+    @staticmethod
+    def forward(fctx, log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, batch_first):
+        lp = log_probs.detach()
+        if lp.stride(2) != 1:
+            lp = lp.contiguous()
+        if batch_first:
+            (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
+        else:
+            (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+        Lmax = targets.shape[1]
+        tg = targets if (Lmax > 0 and targets.stride(1) == 1 and targets.stride(0) >= Lmax) else \
+            (targets.contiguous() if Lmax > 0 else torch.zeros((B, 1), dtype=torch.long, device=lp.device))
+        S_max = 2 * Lmax + 1
+        need = fctx.needs_input_grad[0]
+        nll = torch.empty(B, dtype=torch.float32, device=lp.device)
+        la = torch.empty((B, T, S_max), dtype=torch.float32, device=lp.device) if need else None
+        lb = torch.empty((B, T, S_max), dtype=torch.float32, device=lp.device) if need else None
+        L.check(L.lib().av_ctc_loss_fwd(ptr(lp), sb, st, ptr(tg), tg.stride(0), ptr(input_lengths), ptr(target_lengths), B, T, V, S_max,
+                                        int(blank), int(bool(zero_infinity)), ptr(nll), ptr(la), ptr(lb), stream()), "av_ctc_loss_fwd")
+        if need:
+            fctx.save_for_backward(lp, tg, input_lengths, target_lengths, nll, la, lb)
+            fctx.cfg = (B, T, V, S_max, sb, st, int(blank), bool(batch_first))
+        return nll
+
+    @staticmethod
+    def backward(fctx, g):
+        lp, tg, il, tl, nll, la, lb = fctx.saved_tensors
+        B, T, V, S_max, sb, st, blank, batch_first = fctx.cfg
+        g = g.contiguous().float()
+        grad = torch.empty((B, T, V), dtype=torch.float32, device=lp.device)
+        L.check(L.lib().av_ctc_loss_bwd(ptr(lp), sb, st, ptr(tg), tg.stride(0), ptr(il), ptr(tl), B, T, V, S_max, blank, ptr(nll), ptr(la),
+                                        ptr(lb), ptr(g), ptr(grad), stream()), "av_ctc_loss_bwd")
+        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None
+
+
+def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, reduction: str = "mean",
+             zero_infinity: bool = False, batch_first: bool = False) -> Tensor:
+    """torch.nn.functional.ctc_loss on the HIP kernels: same argument order, defaults and reductions ("mean" = mean over the batch of
+    nll_i / max(L_i, 1), "sum", "none").  ``log_probs`` fp32 [T, B, V] (``batch_first``: [B, T, V]); any view with a contiguous last
+    dimension is taken without a copy.  ``targets`` int64 [B, Lmax], padded (the 1-D concatenated form is not supported).  The
+    lengths may live on the device (nothing is read back) or on the host (copied without blocking).  With ``zero_infinity=False`` an
+    infeasible item returns +inf and its gradient is unspecified (here: zero)."""
+    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
+        raise RuntimeError("ctc_loss (HIP): log_probs must be on the GPU; there is no CPU fallback")
+    if log_probs.dim() != 3:
+        raise ValueError(f"ctc_loss: log_probs must be [T, B, V] (or [B, T, V] with batch_first), got shape {tuple(log_probs.shape)}")
+    if log_probs.dtype != torch.float32:
+        raise TypeError(f"ctc_loss: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError(f"ctc_loss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+    B = log_probs.shape[0 if batch_first else 1]
+    if targets.dim() != 2:
+        raise NotImplementedError("ctc_loss (HIP): targets must be the padded 2-D form [B, Lmax]; 1-D concatenated targets are not supported")
+    if targets.shape[0] != B:
+        raise ValueError(f"ctc_loss: targets has {targets.shape[0]} rows for a batch of {B}")
+    if targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise TypeError(f"ctc_loss: targets must be an integer tensor, got {targets.dtype}")
+    dev = log_probs.device
+    tg = targets.to(device=dev, dtype=torch.long, non_blocking=True)
+    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
+    tl = _ctc_lengths(target_lengths, "target_lengths", B, dev)
+    nll = _CtcLossFn.apply(log_probs, tg, il, tl, int(blank), bool(zero_infinity), bool(batch_first))
+    if reduction == "none":
+        return nll
+    if reduction == "sum":
+        return nll.sum()
+    return (nll / tl.clamp_min(1).to(torch.float32)).mean()
