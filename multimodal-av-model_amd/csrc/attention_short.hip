@@ -487,6 +487,16 @@ __device__ __forceinline__ void drop_quad4(unsigned long long seed, unsigned str
     for (int e = 0; e < 4; ++e) dm[e] = pos == 0 ? got[e][0] : (pos == 1 ? got[e][1] : (pos == 2 ? got[e][2] : got[e][3]));
 }
 
+// A product that is rounded to float32 before it is rounded to the 16-bit type.  The half build otherwise contracts `product -> half` into
+// v_fma_mixlo_f16 (ONE rounding of the exact product) in the instantiations where the multiplier is a plain value and not where it is a
+// select (TWO roundings), and the DROP 1 / DROP 2 backward, which state the same arithmetic, differed in dV by an ulp of half now and then.
+__device__ __forceinline__ float rounded_f32(float x) {
+#ifdef AV_HALF
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+
 // ---------------------------------------------------------------------------------------------------- backward
 template <int DROP>             // 0 none, 1 generated masks, 2 precomputed keep bits
 __global__ __launch_bounds__(NT, 4) void attn_bwd_short_kernel(const BwdP p, int R) {
@@ -590,7 +600,7 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_short_kernel(const BwdP p, int
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {                // vector issue bounds this kernel: one FMA into the exponent, the softmax scale
                     const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], c, kneg - l4[e]));      // multiplies dK^T once at the end
-                    Pt[hf][e] = pv * dm[e];
+                    Pt[hf][e] = DROP ? rounded_f32(pv * dm[e]) : pv;
                     St[hf][e] = pv * __builtin_fmaf(dp[e], dm[e], -d4[e]);
                 }
             }

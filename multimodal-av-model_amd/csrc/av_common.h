@@ -245,8 +245,10 @@ __device__ __forceinline__ void drop_draw(unsigned long long seed, unsigned stre
 }
 // The keep test resolves p to thr = ceil(65536 p) sixteen-bit steps, so the kept fraction is (65536 - thr) / 65536, not 1 - p: the survivors
 // are scaled by the inverse of THAT (an unbiased mask; with 1 / (1 - p) the expectation was off by up to 1.5e-5 relative).
+// p >= 1 - 2^-16 resolves to thr = 65536: nothing is kept (every keep test compares a 16-bit draw with thr), and the factor is clamped to
+// its largest finite step so that 0 x factor stays 0 where a kernel folds it into a normaliser (it was +inf, hence NaN outputs).
 __device__ __host__ __forceinline__ float drop_inv_keep(float p) {
-    const float thr = __builtin_ceilf(p * 65536.0f);
+    const float thr = __builtin_fminf(__builtin_ceilf(p * 65536.0f), 65535.0f);
     return 65536.0f / (65536.0f - thr);
 }
 // the four 16-bit uniforms (as floats in [0,1)) of the aligned group that starts at element idx4 (a multiple of 4)
