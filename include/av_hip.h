@@ -278,6 +278,22 @@ int av_loss_combine(const float* nll, const float* w, const float* c1, const flo
  * [B][T][V], lengths optional int64 [B] (frames to decode); out_ids int32 [B][T] = collapsed ids padded with -1, out_len int32 [B] */
 int av_ctc_greedy(const float* log_probs, const long long* lengths, int* out_ids, int* out_len, int B, int T, int V, int blank,
                   void* stream);
+/* CTC prefix beam search without a language model, n-best (the decoder the reference's beam_search.py:2-48 is named after; opt-in
+ * in evaluate(), trainer.py:230,237): per prefix the blank-ending and non-blank-ending log-masses, equal prefixes merged by content,
+ * the beam_width best kept per frame.  log_probs fp32, element [b][t][v] at b * stride_b + t * stride_t + v; lengths optional
+ * int64 [B] on the DEVICE (frames to consume, clamped to [0, T]); no host synchronisation.  1 <= beam_width <= 64,
+ * 1 <= nbest <= beam_width, T <= 4096, V >= 2, 0 <= blank < V.  out_ids int32 [B][nbest][T] = the hypotheses in descending score
+ * order, each padded with -1; out_len int32 [B][nbest] (-1: fewer than nbest hypotheses exist); out_score fp32 [B][nbest] =
+ * log-likelihood summed over the alignments the search kept.  Equal scores are ordered by candidate id (csrc/ctc_beam.hip).
+ * workspace: av_ctc_beam_workspace_bytes(B, T, V, beam_width) bytes, 8-byte aligned; a smaller one is an error status.
+ * av_ctc_beam_frame_pass (the first of the two passes alone: the beam_width + 1 best non-blank tokens of every consumed frame into the
+ * workspace) is what av_ctc_beam_search runs first; it is exported for tools/beam_timing.py (beam_search.py:2-48). */
+int av_ctc_beam_workspace_bytes(int B, int T, int V, int beam_width, long long* bytes);
+int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, void* workspace,
+                           long long workspace_bytes, int B, int T, int V, int blank, int beam_width, void* stream);
+int av_ctc_beam_search(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
+                       int* out_len, float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V, int blank,
+                       int beam_width, int nbest, void* stream);
 /* CTC loss on the device, opt-in replacement of nn.CTCLoss(blank, zero_infinity=True) (model/trainer.py:25,116-117): the semantics of
  * torch.nn.functional.ctc_loss(..., reduction="none") with padded 2-D targets.  log_probs fp32, element [b][t][v] at
  * b * stride_b + t * stride_t + v (element strides: [B][T][V] and the [T][B][V] view are both taken without a copy); targets int64

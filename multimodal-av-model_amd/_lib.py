@@ -127,6 +127,9 @@ SIGNATURES = {
     "av_reduce_sum": [vp, ll, vp, f32, i32, vp],
     "av_loss_combine": [vp, vp, vp, vp, f32, i32, vp, vp],
     "av_ctc_greedy": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "av_ctc_beam_workspace_bytes": [i32, i32, i32, i32, C.POINTER(ll)],
+    "av_ctc_beam_frame_pass": [vp, ll, ll, vp, vp, ll, i32, i32, i32, i32, i32, vp],
+    "av_ctc_beam_search": [vp, ll, ll, vp, vp, vp, vp, vp, ll, i32, i32, i32, i32, i32, i32, vp],
     "av_ctc_loss_fwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "av_ctc_loss_bwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "av_lip_gray_resize": [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp],

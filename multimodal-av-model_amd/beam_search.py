@@ -3,9 +3,13 @@
 ``simple_beam_search`` there scores raw frame paths additively without prefix merging, so its best beam is
 always the per-frame argmax path: it equals greedy CTC decoding (pinned in tests/golden).  This
 version computes exactly that with one argmax over the whole [T,V] matrix and one host transfer instead of
-T*beam_width ``.item()`` calls."""
+T*beam_width ``.item()`` calls.
+
+``prefix_beam_search`` is what the name promises: CTC prefix beam search without a language model (blank-ending and non-blank-ending
+mass per prefix, equal prefixes merged), n-best, on the device kernels of csrc/ctc_beam.hip for GPU tensors and in numpy for host tensors."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -43,6 +47,105 @@ def greedy_batch(log_probs: torch.Tensor, blank: int, lengths: torch.Tensor = No
             prev = i
         res.append(out)
     return res
+
+
+def _host_prefix_beam(lp: np.ndarray, W: int, blank: int):
+    """One utterance, float32 [T, V] -> (id lists, scores) of the surviving entries in descending score order.  The law and the order of
+    csrc/ctc_beam.hip: per frame only the K = min(W + 1, V - 1) best non-blank tokens (value descending, token ascending) are expanded,
+    plus every extension that lands on a live prefix (compared by content), which is merged into that prefix's stay; candidate
+    slot * (K + 1) + r (r = 0: stay, r >= 1: token of rank r - 1) is ranked by score, equal scores by candidate id."""
+    T, V = lp.shape
+    K = min(W + 1, V - 1)
+    NEG = np.float32(-np.inf)
+    cols = np.delete(np.arange(V), blank)
+    order = np.argsort(-lp[:, cols], axis=1, kind="stable")[:, :K]           # stable: equal values keep the smaller token first
+    top_t = cols[order]                                                       # [T, K]
+    top_v = np.take_along_axis(lp, top_t, axis=1)
+    prefixes = [()]
+    pb, pnb = np.zeros(1, np.float32), np.full(1, NEG, np.float32)
+    last = np.full(1, -1)
+    with np.errstate(invalid="ignore"):
+        for t in range(T):
+            row, n = lp[t], len(prefixes)
+            tot = np.logaddexp(pb, pnb)
+            cand_pb = np.full((n, K + 1), NEG, np.float32)
+            cand_pnb = np.empty((n, K + 1), np.float32)
+            cand_pb[:, 0] = tot + row[blank]
+            cand_pnb[:, 0] = np.where(last >= 0, pnb + row[np.maximum(last, 0)], NEG)
+            cand_pnb[:, 1:] = np.where(top_t[t][None, :] == last[:, None], pb[:, None], tot[:, None]) + top_v[t][None, :]
+            dead = np.zeros((n, K + 1), bool)
+            dead[:, 1:] = np.isnan(top_v[t])[None, :]
+            if n > 1:
+                slot = {p: i for i, p in enumerate(prefixes)}
+                rank = {int(c): r for r, c in enumerate(top_t[t])}
+                for j, p in enumerate(prefixes):
+                    i = slot.get(p[:-1]) if p else None
+                    if i is None:
+                        continue
+                    c = p[-1]                                                  # prefixes[i] + c is prefixes[j]: merge, and drop the duplicate
+                    cand_pnb[j, 0] = np.logaddexp(cand_pnb[j, 0], (pb[i] if last[i] == c else tot[i]) + row[c])
+                    if c in rank:
+                        dead[i, 1 + rank[c]] = True
+            score = np.logaddexp(cand_pb, cand_pnb).ravel()
+            ids = np.flatnonzero(~dead.ravel())
+            ids = ids[np.argsort(-score[ids], kind="stable")[:W]]
+            src, r = np.divmod(ids, K + 1)
+            prefixes = [prefixes[i] if k == 0 else prefixes[i] + (int(top_t[t, k - 1]),) for i, k in zip(src.tolist(), r.tolist())]
+            pb, pnb = cand_pb.ravel()[ids], cand_pnb.ravel()[ids]
+            last = np.where(r == 0, last[src], top_t[t][np.maximum(r - 1, 0)])
+        final = np.logaddexp(pb, pnb)
+    return [list(p) for p in prefixes], [float(x) for x in final]
+
+
+def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False):
+    """CTC prefix beam search without a language model.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
+    B lists of up to ``nbest`` id lists in descending score order (fewer where fewer hypotheses exist); ``return_scores``: (ids, scores)
+    with the scores in the same nesting.  ``lengths`` [B]: frames to consume per item (0 gives the empty hypothesis with score 0).
+
+    GPU tensor: the two kernels of csrc/ctc_beam.hip (strided views with contiguous rows are taken as they are) and ONE transfer of ids,
+    lengths and scores.  Host tensor: the same law in float32 numpy.  Ties: equal scores are ordered by candidate id (ctc_beam.hip)."""
+    W, nbest, blank = int(beam_width), int(nbest), int(blank)
+    if log_probs.dim() == 2:
+        log_probs = log_probs[None]
+    if log_probs.dim() != 3:
+        raise ValueError(f"prefix_beam_search: log_probs must be [B, T, V] or [T, V], got shape {tuple(log_probs.shape)}")
+    B, T, V = log_probs.shape
+    if not 1 <= W <= 64 or not 1 <= nbest <= W:
+        raise ValueError(f"prefix_beam_search: need 1 <= nbest <= beam_width <= 64, got beam_width={W} nbest={nbest}")
+    if V < 2 or not 0 <= blank < V or not 1 <= T <= 4096:
+        raise ValueError(f"prefix_beam_search: need V >= 2, 0 <= blank < V and 1 <= T <= 4096, got T={T} V={V} blank={blank}")
+    if lengths is not None and (not isinstance(lengths, torch.Tensor) or lengths.numel() != B):
+        lengths = torch.as_tensor(lengths, dtype=torch.long).reshape(B)
+    if log_probs.is_cuda:
+        from . import _lib as L
+        from . import ops
+        lp = log_probs.detach()
+        if lp.dtype != torch.float32 or lp.stride(2) != 1 or lp.stride(1) < V or lp.stride(0) < T * lp.stride(1):
+            lp = lp.float().contiguous()
+        ln = None if lengths is None else lengths.to(device=lp.device, dtype=torch.long).contiguous()
+        nbytes = L.ll(0)
+        L.check(L.lib().av_ctc_beam_workspace_bytes(B, T, V, W, L.C.byref(nbytes)), "av_ctc_beam_workspace_bytes")
+        ws = torch.empty((max(1, (nbytes.value + 7) // 8),), dtype=torch.int64, device=lp.device)
+        # one int32 block [B][nbest][T + 2]: ids, then the length, then the score's bits - a single transfer to the host
+        out = torch.empty((B, nbest, T), dtype=torch.int32, device=lp.device)
+        cnt = torch.empty((B, nbest), dtype=torch.int32, device=lp.device)
+        sc = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
+        L.check(L.lib().av_ctc_beam_search(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
+                                           ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, ops.stream()), "av_ctc_beam_search")
+        packed = torch.cat([out, cnt[..., None], sc.view(torch.int32)[..., None]], dim=2).cpu()
+        cnt_h, sc_h = packed[..., T].tolist(), packed[..., T + 1].contiguous().view(torch.float32).tolist()
+        ids = [[packed[b, k, :cnt_h[b][k]].tolist() for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
+        scores = [[sc_h[b][k] for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
+    else:
+        lp_h = log_probs.detach().to(torch.float32).numpy()
+        ln_h = [T] * B if lengths is None else [min(max(int(x), 0), T) for x in lengths.tolist()]
+        ids, scores = [], []
+        for b in range(B):
+            i, s = _host_prefix_beam(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank)
+            ids.append(i[:nbest]); scores.append(s[:nbest])
+    if nbest == 1:
+        ids, scores = [i[0] for i in ids], [s[0] for s in scores]
+    return (ids, scores) if return_scores else ids
 
 
 def fast_decode(ids, tokenizer):

@@ -1,0 +1,370 @@
+// CTC prefix beam search on the device, without a language model (the decoder the reference's beam_search.py:2-48 is named after but
+// does not implement; opt-in in evaluate(), model/trainer.py:230,237 of the reference).  float32 in both libraries.
+//
+// Law.  A beam entry is a prefix l with two log-masses: p_b (alignments ending in blank) and p_nb (ending in last(l)); start {(): (0, -inf)}.
+// Per consumed frame, with tot = p_b (+) p_nb and (+) = logaddexp:
+//   stay:        l   gets p_b' (+)= tot + row[blank], and, if l is not empty, p_nb' (+)= p_nb + row[last(l)]
+//   extend by c: l+c gets p_nb' (+)= (c == last(l) ? p_b : tot) + row[c]                      for every c != blank
+// Contributions to the same prefix BY CONTENT are combined, the W entries with the largest p_b' (+) p_nb' survive.
+//
+// Two facts the kernels rely on (DESIGN "CTC prefix beam search"):
+//  1. Exact token pruning: per frame it is enough to extend by the W + 1 best non-blank tokens plus, for every live prefix l, every token c
+//     for which l+c is itself live.  The second clause is the merge of an extension into a live entry; without it merged mass is lost.
+//  2. Prefix identity is by content, not by arena node: l+c can drop out of the beam while l+c+d survives, and a later re-extension of l by c
+//     makes a second node for the same prefix.  Prefixes are compared by (length, last token, 64-bit hash).  The hash is a chain of a
+//     64-bit bijective mixer (splitmix64's finaliser) over the tokens, so two different prefixes of one length collide with probability
+//     about 2^-64 per compared pair; a frame compares at most W^2 = 2^12 pairs, an utterance at most T W^2 <= 2^24: below 2^-40 per utterance
+//     at the largest supported shape.
+//
+// Two passes.  Frame pass: grid over (b, t), one wave per row; the row is read once and its K = min(W + 1, V - 1) best non-blank
+// (value, token) pairs go to the workspace in the order (value descending, token ascending).  Search pass: one workgroup of 256 threads per
+// utterance, sequential in t, beam state in LDS; per frame it resolves the merges, forms the n (K + 1) candidates (candidate id =
+// slot * (K + 1) + r; r = 0: stay, r >= 1: extension by the token of rank r - 1), selects the W best with a 4 x 8-bit radix select on
+// the order-preserving integer image of the score and stores them in rank order, so the beam is always sorted.
+//
+// Tie rule: equal scores are ordered by candidate id, ascending (a function of the inputs alone: slots are in rank order, ranks of tokens
+// are (value descending, token ascending)).  Everything is deterministic: no floating-point atomics, no order that depends on scheduling.
+#include "av_common.h"
+
+namespace {
+
+constexpr int MAXT = 4096;
+constexpr int MAXW = 64;
+constexpr int MAXK = MAXW + 1;
+constexpr int MAXCAND = MAXW * (MAXK + 1);          // W (W + 2)
+constexpr int ROW_REGS = 16;                        // a row of V <= 64 * 16 floats is held in registers by the frame pass
+
+struct BeamWorkspace {
+    long long topv, topt, apar, atok, total;        // byte offsets: top values fp32 [B][T][W+1], top tokens int32 [B][T][W+1], arena int32 [B][T][W] x 2
+};
+
+static BeamWorkspace beam_workspace(long long B, long long T, long long W) {
+    BeamWorkspace w;
+    const long long top = B * T * (W + 1) * 4, arena = B * T * W * 4;
+    w.topv = 0; w.topt = top; w.apar = 2 * top; w.atok = 2 * top + arena; w.total = 2 * top + 2 * arena;
+    return w;
+}
+
+__device__ __forceinline__ float logaddexp_f(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == -INFINITY) return -INFINITY;           // (-inf) (+) (-inf): never NaN
+    return m + log1pf(expf(-fabsf(a - b)));
+}
+
+// order-preserving image of a float in the unsigned integers; 0 is below every float (-inf maps to 0x007fffff) and marks "no candidate"
+__device__ __forceinline__ unsigned key_of(float x) {
+    const unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float score_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) {
+    unsigned long long z = h + 0x9E3779B97F4A7C15ull * (unsigned long long)(c + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// (value, token) a precedes (value, token) b in the frame pass's order
+__device__ __forceinline__ bool before(float av, int at, float bv, int bt) { return av > bv || (av == bv && at < bt); }
+
+// ---- frame pass: the K best non-blank tokens of every consumed row ----
+__global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const float* __restrict__ lp, long long stride_b, long long stride_t,
+                                                             const long long* __restrict__ lengths, float* __restrict__ topv,
+                                                             int* __restrict__ topt, int T, int V, int blank, int K, int K1) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+    if (t >= T) return;
+    int Tb = lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
+    if (t >= Tb) return;
+    const float* row = lp + (long long)b * stride_b + (long long)t * stride_t;
+    const bool in_regs = V <= 64 * ROW_REGS;
+    float r[ROW_REGS];
+    if (in_regs) {
+#pragma unroll
+        for (int j = 0; j < ROW_REGS; ++j) {
+            const int v = lane + 64 * j;
+            r[j] = v < V ? row[v] : 0.f;
+        }
+    }
+    float pv = INFINITY;                            // the previous pick: the next one is the first entry strictly after it in the order
+    int pt = -1;
+    const long long o = ((long long)b * T + t) * K1;
+    for (int k = 0; k < K; ++k) {
+        float bv = 0.f;
+        int bt = 0x7fffffff;                        // none yet
+        if (in_regs) {
+#pragma unroll
+            for (int j = 0; j < ROW_REGS; ++j) {
+                const int v = lane + 64 * j;
+                const float x = r[j];
+                if (v < V && v != blank && before(pv, pt, x, v) && (bt == 0x7fffffff || before(x, v, bv, bt))) { bv = x; bt = v; }
+            }
+        } else {
+            for (int v = lane; v < V; v += 64) {
+                const float x = row[v];
+                if (v != blank && before(pv, pt, x, v) && (bt == 0x7fffffff || before(x, v, bv, bt))) { bv = x; bt = v; }
+            }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const float ov = __shfl_xor(bv, s, 64);
+            const int ot = __shfl_xor(bt, s, 64);
+            if (ot != 0x7fffffff && (bt == 0x7fffffff || before(ov, ot, bv, bt))) { bv = ov; bt = ot; }
+        }
+        const bool none = bt == 0x7fffffff;         // fewer than K comparable entries (NaN in the row): the rest of the list is empty
+        if (lane == 0) { topv[o + k] = none ? -INFINITY : bv; topt[o + k] = none ? -1 : bt; }
+        if (none) {
+            for (int k2 = k + 1 + lane; k2 < K; k2 += 64) { topv[o + k2] = -INFINITY; topt[o + k2] = -1; }
+            break;
+        }
+        pv = bv; pt = bt;
+    }
+}
+
+// ---- search pass ----
+struct BeamState {
+    float pb[MAXW], pnb[MAXW];
+    int last[MAXW], len[MAXW], node[MAXW];
+    unsigned long long hash[MAXW];
+};
+
+// inclusive prefix sum of one int per thread over the 256 threads of the workgroup (wsum: 4 ints of LDS); ends with the data visible
+__device__ __forceinline__ int block_scan_incl(int v, int* wsum) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int o = __shfl_up(v, s, 64);
+        if (lane >= s) v += o;
+    }
+    __syncthreads();                                // the previous use of wsum is over
+    if (lane == 63) wsum[w] = v;
+    __syncthreads();
+    for (int i = 0; i < w; ++i) v += wsum[i];
+    return v;
+}
+
+__global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ lp, long long stride_b, long long stride_t,
+                                                              const long long* __restrict__ lengths, const float* __restrict__ topv,
+                                                              const int* __restrict__ topt, int* __restrict__ apar, int* __restrict__ atok,
+                                                              int* __restrict__ out_ids, int* __restrict__ out_len,
+                                                              float* __restrict__ out_score, int T, int V, int blank, int W, int K, int K1,
+                                                              int nbest) {
+    __shared__ BeamState st[2];
+    __shared__ unsigned keys[MAXCAND];
+    __shared__ float tot[MAXW], rlast[MAXW], spb[MAXW], spnb[MAXW], tokv[MAXK];
+    __shared__ int tokt[MAXK], parent[MAXW], mrank[MAXW], sel[MAXW], hist[256], wsum[4], pick[2], nvalid;
+    __shared__ unsigned selkey[MAXW];
+    __shared__ float rblank;
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Tb = lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
+    const float* base = lp + (long long)b * stride_b;
+    const long long tb = (long long)b * T;
+    const int C = K + 1;                             // candidates per live entry
+
+    if (tid == 0) {
+        st[0].pb[0] = 0.f; st[0].pnb[0] = -INFINITY; st[0].last[0] = -1; st[0].len[0] = 0; st[0].node[0] = -1; st[0].hash[0] = 0;
+    }
+    int n = 1;
+    // the top list of the next frame travels in registers while the current frame is searched
+    float nv = -INFINITY;
+    int nt = -1;
+    if (tid < K && Tb > 0) { nv = topv[tb * K1 + tid]; nt = topt[tb * K1 + tid]; }
+    __syncthreads();
+
+    for (int t = 0; t < Tb; ++t) {
+        const BeamState& cur = st[t & 1];
+        BeamState& nxt = st[(t & 1) ^ 1];
+        const float* row = base + (long long)t * stride_t;
+        // 1. this frame's inputs
+        if (tid < K) { tokv[tid] = nv; tokt[tid] = nt; }
+        if (tid < K && t + 1 < Tb) { nv = topv[(tb + t + 1) * K1 + tid]; nt = topt[(tb + t + 1) * K1 + tid]; }
+        if (tid >= 64 && tid < 64 + n) {
+            const int i = tid - 64, c = cur.last[i];
+            rlast[i] = c >= 0 ? row[c] : -INFINITY;
+            tot[i] = logaddexp_f(cur.pb[i], cur.pnb[i]);
+            parent[i] = -1; mrank[i] = -1;
+        }
+        if (tid == 128) { rblank = row[blank]; nvalid = 0; }
+        __syncthreads();
+        // 2. merges by content: entry j is the extension of entry i by last(j)
+        for (int p = tid; p < n * n; p += 256) {
+            const int j = p / n, i = p - j * n;
+            if (cur.len[j] == cur.len[i] + 1 && cur.hash[j] == hash_push(cur.hash[i], cur.last[j])) {
+                parent[j] = i;                       // at most one i per j: live prefixes are distinct
+                const int c = cur.last[j];
+                int r = -1;
+                for (int k = 0; k < K; ++k) if (tokt[k] == c) r = k;
+                mrank[j] = r;
+            }
+        }
+        __syncthreads();
+        // 3. candidate scores
+        const int N = n * C;
+        for (int q = tid; q < N; q += 256) {
+            const int i = q / C, r = q - i * C;
+            float s;
+            if (r == 0) {
+                const float pb = tot[i] + rblank;
+                float pnb = cur.len[i] > 0 ? cur.pnb[i] + rlast[i] : -INFINITY;
+                const int pi = parent[i];
+                if (pi >= 0) pnb = logaddexp_f(pnb, (cur.last[pi] == cur.last[i] ? cur.pb[pi] : tot[pi]) + rlast[i]);
+                spb[i] = pb; spnb[i] = pnb;
+                s = logaddexp_f(pb, pnb);
+                keys[q] = key_of(s);
+            } else {
+                const int c = tokt[r - 1];
+                s = (c == cur.last[i] ? cur.pb[i] : tot[i]) + tokv[r - 1];
+                keys[q] = c >= 0 ? key_of(s) : 0u;
+            }
+        }
+        __syncthreads();
+        if (tid < n && parent[tid] >= 0 && mrank[tid] >= 0) keys[parent[tid] * C + 1 + mrank[tid]] = 0u;      // merged into entry tid's stay
+        // 4. the want-th largest key: radix select, 8 bits a pass
+        const int want = min(W, N);
+        unsigned prefix = 0, mask = 0;
+        int remaining = want;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();                         // also orders the write of step 3's tail before the first read of keys
+            for (int q = tid; q < N; q += 256) {
+                const unsigned k = keys[q];
+                if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            const int h = hist[255 - tid];
+            const int incl = block_scan_incl(h, wsum);         // entries in digits >= 255 - tid
+            if (incl - h < remaining && remaining <= incl) { pick[0] = 255 - tid; pick[1] = remaining - (incl - h); }
+            __syncthreads();
+            prefix |= (unsigned)pick[0] << shift; mask |= 255u << shift;
+            remaining = pick[1];
+        }
+        // prefix = the want-th largest key; take every key above it and the first `remaining` equal to it, in candidate order
+        const int per = (N + 255) / 256, q0 = tid * per, q1 = min(N, q0 + per);
+        int gt = 0, eq = 0;
+        for (int q = q0; q < q1; ++q) { const unsigned k = keys[q]; gt += k > prefix; eq += k == prefix; }
+        const int packed = block_scan_incl(gt | (eq << 16), wsum);
+        if (tid == 255) pick[0] = packed & 0xffff;   // all keys above the threshold
+        __syncthreads();
+        {
+            const int ngt = pick[0];
+            int og = (packed & 0xffff) - gt, oe = (packed >> 16) - eq;
+            for (int q = q0; q < q1; ++q) {
+                const unsigned k = keys[q];
+                if (k > prefix) { sel[og] = q; selkey[og] = k; ++og; }
+                else if (k == prefix) { if (oe < remaining) { sel[ngt + oe] = q; selkey[ngt + oe] = k; } ++oe; }
+            }
+        }
+        __syncthreads();
+        // 5. rank the selected entries (key descending, candidate id ascending) and store them in that order
+        if (tid < want) {
+            const unsigned k = selkey[tid];
+            const int q = sel[tid];
+            int rank = 0;
+            for (int u = 0; u < want; ++u) rank += selkey[u] > k || (selkey[u] == k && sel[u] < q);
+            if (k != 0u) {
+                atomicAdd(&nvalid, 1);
+                const int i = q / C, r = q - i * C;
+                if (r == 0) {
+                    nxt.pb[rank] = spb[i]; nxt.pnb[rank] = spnb[i]; nxt.last[rank] = cur.last[i]; nxt.len[rank] = cur.len[i];
+                    nxt.node[rank] = cur.node[i]; nxt.hash[rank] = cur.hash[i];
+                } else {
+                    const int c = tokt[r - 1];
+                    const long long node = (tb + t) * W + rank;
+                    apar[node] = cur.node[i]; atok[node] = c;
+                    nxt.pb[rank] = -INFINITY; nxt.pnb[rank] = score_of(k); nxt.last[rank] = c; nxt.len[rank] = cur.len[i] + 1;
+                    nxt.node[rank] = t * W + rank; nxt.hash[rank] = hash_push(cur.hash[i], c);
+                }
+            }
+        }
+        __syncthreads();
+        n = nvalid;                                  // invalid candidates have the lowest key: the valid ones fill slots 0 .. n-1
+        __syncthreads();                             // nvalid is reset by the next frame's step 1
+    }
+
+    // 6. emit: entries are in rank order; walk the back-pointers of the first nbest
+    const BeamState& fin = st[Tb & 1];
+    int* ids = out_ids + (long long)b * nbest * T;
+    if (tid < nbest) {
+        int len = -1;                                // fewer than nbest hypotheses exist: length -1, score -inf
+        float score = -INFINITY;
+        if (tid < n) {
+            len = fin.len[tid];
+            score = logaddexp_f(fin.pb[tid], fin.pnb[tid]);
+            int node = fin.node[tid];
+            for (int p = len - 1; p >= 0 && node >= 0; --p) {
+                ids[(long long)tid * T + p] = atok[tb * W + node];
+                node = apar[tb * W + node];
+            }
+        }
+        out_len[b * nbest + tid] = len;
+        out_score[b * nbest + tid] = score;
+        sel[tid] = len;
+    }
+    __syncthreads();
+    for (int x = tid; x < nbest * T; x += 256) {
+        const int k = x / T, p = x - k * T;
+        if (p >= sel[k]) ids[x] = -1;
+    }
+}
+
+}  // namespace
+
+extern "C" int av_ctc_beam_workspace_bytes(int B, int T, int V, int beam_width, long long* bytes) {
+    AV_CHECK(bytes, "av_ctc_beam_workspace_bytes: null pointer");
+    AV_CHECK(B >= 0 && T >= 1 && T <= MAXT && V >= 2, "av_ctc_beam_workspace_bytes: bad shape B=%d T=%d V=%d (1 <= T <= %d, V >= 2)", B, T, V, MAXT);
+    AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "av_ctc_beam_workspace_bytes: beam_width %d outside [1, %d]", beam_width, MAXW);
+    *bytes = beam_workspace(B, T, beam_width).total;
+    return AV_OK;
+}
+
+// argument checks shared by the two launching entry points
+static int beam_check(const char* who, const float* log_probs, long long stride_b, long long stride_t, void* workspace,
+                      long long workspace_bytes, int B, int T, int V, int blank, int beam_width) {
+    AV_CHECK(log_probs && workspace, "%s: null pointer", who);
+    AV_CHECK(B >= 0 && B <= 65535 && T >= 1 && T <= MAXT && V >= 2, "%s: bad shape B=%d T=%d V=%d (B <= 65535, 1 <= T <= %d, V >= 2)", who, B,
+             T, V, MAXT);
+    AV_CHECK(blank >= 0 && blank < V, "%s: blank %d outside [0, %d)", who, blank, V);
+    AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "%s: beam_width %d outside [1, %d]", who, beam_width, MAXW);
+    AV_CHECK(stride_t >= V && stride_b >= (long long)T * stride_t, "%s: strides (%lld, %lld) overlap rows of [%d][%d][%d]", who, stride_b,
+             stride_t, B, T, V);
+    const long long need = beam_workspace(B, T, beam_width).total;
+    AV_CHECK(workspace_bytes >= need, "%s: workspace of %lld bytes is too small, %lld needed", who, workspace_bytes, need);
+    return AV_OK;
+}
+
+extern "C" int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths,
+                                      void* workspace, long long workspace_bytes, int B, int T, int V, int blank, int beam_width,
+                                      void* stream) {
+    const int rc = beam_check("av_ctc_beam_frame_pass", log_probs, stride_b, stride_t, workspace, workspace_bytes, B, T, V, blank, beam_width);
+    if (rc != AV_OK) return rc;
+    if (B == 0) return AV_OK;
+    const BeamWorkspace w = beam_workspace(B, T, beam_width);
+    const int K1 = beam_width + 1, K = K1 < V - 1 ? K1 : V - 1;      // W + 1 > V - 1: every non-blank token is expanded
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(ctc_beam_frame_kernel, dim3((T + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, log_probs, stride_b, stride_t, lengths,
+                       (float*)(ws + w.topv), (int*)(ws + w.topt), T, V, blank, K, K1);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_ctc_beam_search(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
+                                  int* out_len, float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V,
+                                  int blank, int beam_width, int nbest, void* stream) {
+    AV_CHECK(out_ids && out_len && out_score, "av_ctc_beam_search: null pointer");
+    int rc = beam_check("av_ctc_beam_search", log_probs, stride_b, stride_t, workspace, workspace_bytes, B, T, V, blank, beam_width);
+    if (rc != AV_OK) return rc;
+    AV_CHECK(nbest >= 1 && nbest <= beam_width, "av_ctc_beam_search: nbest %d outside [1, beam_width %d]", nbest, beam_width);
+    if (B == 0) return AV_OK;
+    rc = av_ctc_beam_frame_pass(log_probs, stride_b, stride_t, lengths, workspace, workspace_bytes, B, T, V, blank, beam_width, stream);
+    if (rc != AV_OK) return rc;
+    const BeamWorkspace w = beam_workspace(B, T, beam_width);
+    const int K1 = beam_width + 1, K = K1 < V - 1 ? K1 : V - 1;
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, log_probs, stride_b, stride_t, lengths,
+                       (const float*)(ws + w.topv), (const int*)(ws + w.topt), (int*)(ws + w.apar), (int*)(ws + w.atok), out_ids, out_len,
+                       out_score, T, V, blank, beam_width, K, K1, nbest);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .. import _lib as L
-from ..beam_search import fast_decode, greedy_batch
+from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
 from ..contrastive import contrastive_loss_with_mask
 from ..optim import AvAdam, AvGradScaler
 from ..parallel.dp import GradArena, GradBucketReducer
@@ -73,7 +73,8 @@ class _CombineFn(torch.autograd.Function):
 class MultimodalTrainer:
     def __init__(self, visual_encoder, audio_encoder, fusion_module, decoder1, tokenizer, learning_rate=1e-4, device="cuda",
                  lambda_=0.1, audio_passes: Optional[int] = None, reducer: Optional[GradBucketReducer] = None, pair_batched: bool = True,
-                 visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None):
+                 visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None,
+                 eval_beam_width: Optional[int] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -93,6 +94,11 @@ class MultimodalTrainer:
         # AVAMD_NATIVE_CTC (default "0") here.  Lengths and targets stay on the device: the step then holds no synchronising call and
         # ignores the host copies ``_ctc_input_lengths`` / ``_ctc_target_lengths`` of host_metadata()
         self.native_ctc = ops.native_ctc_default() if native_ctc is None else bool(native_ctc)
+        # opt-in: evaluate() decodes with CTC prefix beam search of this width (beam_search.prefix_beam_search, csrc/ctc_beam.hip).  None reads
+        # AVAMD_EVAL_BEAM (default "0") here; 0 = the greedy decode, which is what the reference's simple_beam_search computes
+        self.eval_beam_width = int(os.environ.get("AVAMD_EVAL_BEAM", "0")) if eval_beam_width is None else int(eval_beam_width)
+        if self.eval_beam_width < 0:
+            raise ValueError(f"eval_beam_width must be >= 0, got {self.eval_beam_width}")
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.optimizer = AvAdam([
@@ -424,7 +430,10 @@ class MultimodalTrainer:
                 out = self.forward_losses(batch)
                 total_loss += (out["loss1"].item() + out["loss2"].item()) / 2
                 for spk, lp, refs, hyps in (("1", out["log_probs1"], refs1, hyps1), ("2", out["log_probs2"], refs2, hyps2)):
-                    ids = greedy_batch(lp, self.tokenizer.blank_id)       # == simple_beam_search best beam
+                    if self.eval_beam_width > 0:
+                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id)
+                    else:
+                        ids = greedy_batch(lp, self.tokenizer.blank_id)   # == simple_beam_search best beam
                     txt, tl = batch["text" + spk], batch["text" + spk + "_lengths"]
                     for i, seq in enumerate(ids):
                         hyps.append(fast_decode(seq, self.tokenizer))
