@@ -443,21 +443,27 @@ def test_trainer_loss_scaling_step_equals_plain_step():
             assert float((sa[k].float() - sb[k].float()).abs().max()) < tol, k
 
 
-@pytest.mark.parametrize("regularize", [False, True])
+@pytest.mark.parametrize("regularize", [False, True, "keep_bits"])
 def test_native_layer_forward_equals_the_per_kernel_path(regularize):
     """av_w2v2_layer_fwd (csrc/w2v2_layer.hip: the seven launches of an encoder layer's forward from one native call) against the per-kernel
     path of model/w2v2.py on the same weights, input, seeds and LayerDrop draws: outputs, mid-layer average and every tensor saved for the
-    backward are bit-identical; the backward then gives bit-identical gradients."""
+    backward are bit-identical; the backward then gives bit-identical gradients.  ``keep_bits``: the regularised case at head dimension 64,
+    the only one where the attention-dropout keep bits are made once on the side stream (ops.attention_mask_shape_ok) and each path waits
+    for them at its own place.  (Against DROP_BITS off the outputs agree to bf16 rounding only: the kernels that read keep bits round
+    differently from the ones that generate their masks, see test_attention_precomputed_dropout_bits_equal_generated_masks.)"""
     init = pkg("utils.init"); enc = pkg("model.encoder"); synth = pkg("dataset.synthetic"); w2 = pkg("model.w2v2")
     pkg("precision").set_precision("bf16")
     extra = dict(hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, layerdrop=0.2, mask_time_prob=0.05) if regularize else {}
+    keep_bits = regularize == "keep_bits"
+    base = dict(init.W2V2_TINY, hidden_size=128, num_attention_heads=2, intermediate_size=256) if keep_bits else init.W2V2_TINY
     outs = []
+    before = w2.NATIVE_LAYER, w2.DROP_BITS
     for native in (2, 0):                                       # 2 = always (the default takes it up to NATIVE_MAX_ROWS tokens per pass), 0 = never
-        w2.NATIVE_LAYER = native
+        w2.NATIVE_LAYER, w2.DROP_BITS = native, keep_bits or before[1]
         try:
-            cfg = dict(init.W2V2_TINY, **extra)
+            cfg = dict(base, **extra)
             ae = enc.AudioEncoder(cfg, freeze=True).cuda()
-            ae.load_state_dict(init.w2v2_state_dict(init.W2V2_TINY))
+            ae.load_state_dict(init.w2v2_state_dict(base))
             for n, p in ae.model.named_parameters():
                 p.requires_grad = any(f"encoder.layers.{i}." in n for i in range(6, 10))
             ae.train()
@@ -467,8 +473,11 @@ def test_native_layer_forward_equals_the_per_kernel_path(regularize):
             (last.float().square().mean() + 0.5 * mid.float().square().mean()).backward()
             grads = {n: p.grad.clone() for n, p in ae.model.named_parameters() if p.grad is not None}
             outs.append((last.detach().clone(), mid.detach().clone(), grads))
+            if keep_bits:                                       # the bits were really made: the shape qualifies and their stream exists
+                assert pkg("ops").attention_mask_shape_ok(torch.bfloat16, *last.shape[:2], last.shape[1], 64)
+                assert getattr(ae.model, "_mask_stream", None) is not None
         finally:
-            w2.NATIVE_LAYER = 1
+            w2.NATIVE_LAYER, w2.DROP_BITS = before
     (l0, m0, g0), (l1, m1, g1) = outs
     assert torch.equal(l0, l1) and torch.equal(m0, m1)
     assert g0.keys() == g1.keys() and len(g0) > 0
