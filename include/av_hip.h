@@ -310,6 +310,25 @@ int av_ctc_loss_fwd(const float* log_probs, long long stride_b, long long stride
 int av_ctc_loss_bwd(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
                     const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
                     const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll, float* grad, void* stream);
+/* CTC forced alignment on the device: the best frame path (Viterbi) of each transcript through the CTC lattice of the log-probs and
+ * lengths the trainer hands to its loss and decoder (model/trainer.py:116-117, 229-242), for word timestamps and alignment scores.
+ * log_probs, strides, targets, target_ld, lengths, the clamping of T_b / L_b and odd S_max = 2 Lmax + 1 are as for av_ctc_loss_fwd
+ * ([B][T][V] and the [T][B][V] view are both taken without a copy; labels and lengths are read from DEVICE memory, no synchronisation);
+ * 1 <= T <= 4096.  The law (csrc/ctc_align.hip): d[t][s] = max(d[t-1][s], d[t-1][s-1], skip ? d[t-1][s-2] : -inf) + lp[t][l'_s] in
+ * fp32, ties to the smaller move, final state S-1 only if strictly better than S-2.  An item is infeasible if a label is outside
+ * [0, V) or EQUAL TO THE BLANK (the loss accepts that; its path could not collapse to the target) or if its final score is -inf.
+ * out_state int32 [B][T]: extended-state index per frame, -1 for t >= T_b and for every frame of an infeasible item;
+ * out_span int32 [B][Lmax][2]: first frame and end frame (exclusive) of target position j (the frames of state 2j+1: contiguous and
+ *   non-empty), -1, -1 for j >= L_b and for infeasible items;  out_token_score fp32 [B][Lmax]: sum of lp[t][l_j] over the span, added in
+ *   frame order, 0 where the span is -1 (both may be NULL when Lmax = 0);
+ * out_score fp32 [B]: the path's log-probability, -inf if infeasible (T_b = 0 with L_b = 0: 0 and an empty path).
+ * workspace: av_ctc_align_workspace_bytes(B, T, S_max) bytes (two bits per frame and state), 4-byte aligned; a smaller one is an error
+ * status.  LDS: that of av_ctc_loss_fwd plus 2 T bytes for the path, same 64 KiB limit.  Deterministic: no atomics. */
+int av_ctc_align_workspace_bytes(int B, int T, int S_max, long long* bytes);
+int av_ctc_align(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
+                 const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
+                 int* out_state, int* out_span, float* out_token_score, float* out_score, void* workspace, long long workspace_bytes,
+                 void* stream);
 /* device side of the input pipeline (dataset/multi_speaker_dataset.py:13-59; decoding wav / npy files stays on the host):
  * av_lip_gray_resize: src [T][Hs][Ws][C] (uint8 if src_is_u8 else fp32) -> dst fp32 [T][Hd][Wd] = bilinear(mean over C) / divisor
  *   (:49-58: .astype(float32).mean(-1), cv2.resize INTER_LINEAR law, / 255), float32 operation order of the reference;

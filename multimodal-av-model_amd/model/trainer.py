@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .. import _lib as L
+from ..align import forced_align, word_segments
 from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
 from ..contrastive import contrastive_loss_with_mask
 from ..optim import AvAdam, AvGradScaler
@@ -448,3 +449,36 @@ class MultimodalTrainer:
         print(f"[Eval] WER1: {wer1:.3f}, WER2: {wer2:.3f}, Avg: {avg_wer:.3f}, Loss: {avg_loss:.4f}")
         self.last_decoded = (hyps1, hyps2)
         return avg_loss, avg_wer
+
+    @torch.no_grad()
+    def align(self, batch, frame_rate: float = 25.0):
+        """Word times of both speakers' transcripts in one batch: CTC forced alignment (align.forced_align, csrc/ctc_align.hip) of
+        ``text*`` against the log-probs of ONE forward_losses call in eval mode.  Returns (segments1, segments2): per utterance the
+        ``align.word_segments`` list ([] for a transcript that cannot be aligned).  The CTC head runs at the lip-frame rate, so
+        ``frame_rate`` is the video's.  One device-to-host transfer per speaker; every module's train / eval mode is restored."""
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("MultimodalTrainer.align: the model runs on the GPU; there is no CPU fallback")
+        mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+        modes = [(sm, sm.training) for m in mods for sm in m.modules()]      # per sub-module: a frozen part may sit in eval mode
+        for m in mods:
+            m.eval()
+        lam, self.lambda_ = self.lambda_, 0.0              # as evaluate(): no contrastive term (and no projection layer is created)
+        try:
+            out = self.forward_losses(batch)
+            if self.native_ctc:
+                self.fusion_module.drain_flag_check()
+            res = []
+            for spk in ("1", "2"):
+                txt, tl = batch["text" + spk], batch["text" + spk + "_lengths"]
+                al = forced_align(out["log_probs" + spk], txt, out["input_lengths" + spk], tl, blank=self.tokenizer.blank_id)
+                # spans and the token scores' bits in one int32 block [B][Lmax][3]: a single transfer
+                packed = torch.cat([al.spans, al.token_scores.view(torch.int32)[..., None]], dim=2).cpu()
+                spans, tok = packed[..., :2], packed[..., 2].contiguous().view(torch.float32)
+                txt_h, tl_h = txt.cpu(), tl.cpu().tolist()
+                res.append([word_segments(self.tokenizer, txt_h[i, :max(0, int(tl_h[i]))], spans[i], tok[i], frame_rate)
+                            for i in range(txt_h.shape[0])])
+        finally:
+            self.lambda_ = lam
+            for sm, was in modes:
+                sm.training = was
+        return tuple(res)

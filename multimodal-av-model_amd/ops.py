@@ -637,3 +637,50 @@ def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, 
     if reduction == "sum":
         return nll.sum()
     return (nll / tl.clamp_min(1).to(torch.float32)).mean()
+
+
+def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, batch_first: bool = False):
+    """CTC forced alignment on the kernel of csrc/ctc_align.hip, arguments as for ``ctc_loss``: ``log_probs`` fp32 [T, B, V]
+    (``batch_first``: [B, T, V]), any view with a contiguous last dimension is taken without a copy; ``targets`` integer [B, Lmax], padded;
+    lengths on the device (nothing is read back) or on the host (copied without blocking).  Returns (states int32 [B, T], spans int32
+    [B, Lmax, 2], token_scores fp32 [B, Lmax], score fp32 [B]) on the device; the law and the outputs of an infeasible item: align.py."""
+    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
+        raise RuntimeError("ctc_align (HIP): log_probs must be on the GPU; there is no CPU fallback")
+    if log_probs.dim() != 3:
+        raise ValueError(f"ctc_align: log_probs must be [T, B, V] (or [B, T, V] with batch_first), got shape {tuple(log_probs.shape)}")
+    if log_probs.dtype != torch.float32:
+        raise TypeError(f"ctc_align: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
+    if targets.dim() != 2 or targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise TypeError(f"ctc_align: targets must be an integer tensor [B, Lmax], got {targets.dtype} {tuple(targets.shape)}")
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    if batch_first:
+        (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
+    else:
+        (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+    if targets.shape[0] != B:
+        raise ValueError(f"ctc_align: targets has {targets.shape[0]} rows for a batch of {B}")
+    dev = lp.device
+    Lmax = targets.shape[1]
+    tg = targets.to(device=dev, dtype=torch.long, non_blocking=True)
+    if Lmax == 0:
+        tg = torch.zeros((B, 1), dtype=torch.long, device=dev)
+    elif tg.stride(1) != 1 or tg.stride(0) < Lmax:
+        tg = tg.contiguous()
+    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
+    tl = _ctc_lengths(target_lengths, "target_lengths", B, dev)
+    S_max = 2 * Lmax + 1
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    tok = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    if B == 0:
+        return states, spans, tok, score
+    need = L.ll(0)
+    L.check(L.lib().av_ctc_align_workspace_bytes(B, T, S_max, C.byref(need)), "av_ctc_align_workspace_bytes")
+    ws = torch.empty((max(1, (need.value + 3) // 4),), dtype=torch.int32, device=dev)
+    L.check(L.lib().av_ctc_align(ptr(lp), sb, st, ptr(tg), tg.stride(0), ptr(il), ptr(tl), B, T, V, S_max, int(blank), ptr(states),
+                                 ptr(spans) if Lmax else None, ptr(tok) if Lmax else None, ptr(score), ptr(ws), ws.numel() * 4, stream()),
+            "av_ctc_align")
+    return states, spans, tok, score
