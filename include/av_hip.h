@@ -278,7 +278,7 @@ int av_loss_combine(const float* nll, const float* w, const float* c1, const flo
  * [B][T][V], lengths optional int64 [B] (frames to decode); out_ids int32 [B][T] = collapsed ids padded with -1, out_len int32 [B] */
 int av_ctc_greedy(const float* log_probs, const long long* lengths, int* out_ids, int* out_len, int B, int T, int V, int blank,
                   void* stream);
-/* CTC prefix beam search without a language model, n-best (the decoder the reference's beam_search.py:2-48 is named after; opt-in
+/* CTC prefix beam search without a language model (with one: av_ctc_beam_search_lm below), n-best (the decoder the reference's beam_search.py:2-48 is named after; opt-in
  * in evaluate(), trainer.py:230,237): per prefix the blank-ending and non-blank-ending log-masses, equal prefixes merged by content,
  * the beam_width best kept per frame.  log_probs fp32, element [b][t][v] at b * stride_b + t * stride_t + v; lengths optional
  * int64 [B] on the DEVICE (frames to consume, clamped to [0, T]); no host synchronisation.  1 <= beam_width <= 64,
@@ -294,6 +294,30 @@ int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b, long long
 int av_ctc_beam_search(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
                        int* out_len, float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V, int blank,
                        int beam_width, int nbest, void* stream);
+/* Token n-gram language model (lm.py: NGramLM) and CTC prefix beam search with its shallow fusion (csrc/ctc_beam_lm.hip).
+ * Tables: lm_unigrams fp32 [lm_vocab + 1][2] = (logp, backoff), natural log, row lm_vocab = begin of sentence; lm_table = lm_slots
+ * 16-byte slots {u64 key, f32 logp, f32 backoff}, 16-byte aligned, lm_slots a power of two, key 0 = empty, linear probing from
+ * splitmix64(key) & (lm_slots - 1), every stored key within lm_probe_bound probes (lookups make no more, at masked indices); keys = the
+ * n-gram's tokens oldest first as id + 1 in 16-bit fields.  1 <= lm_order <= 4, 2 <= lm_vocab <= 65533, lm_bos = lm_vocab or -1 (none).
+ * s(c | ctx): for m from min(lm_order - 1, tokens available) down to 1, the (m + 1)-gram's logp if it is stored, else add the context
+ * m-gram's backoff (nothing if absent) and shorten the context; at m = 0 the unigram.  float32 additions in that order only: the bits of
+ * NGramLM.score.
+ * av_ngram_score: ids int32 [B][Lmax], lens optional int64 [B] on the device (clamped to [0, Lmax]); out fp32 [B][Lmax],
+ * out[b][i] = s(ids[b][i] | ids[b][<i]) for i < lens[b], 0 after; an id outside [0, lm_vocab) gives NaN at its place and matches
+ * nothing as context.  One thread per token.
+ * av_ctc_beam_search_lm: the arguments and outputs of av_ctc_beam_search, and: an entry also carries g = sum over its tokens of
+ * (lm_weight * s(token | tokens before it) + token_bonus), each operation rounded to fp32 on its own; entries are ranked by
+ * (p_b (+) p_nb) + g, which is out_score; out_lm_score fp32 [B][nbest] = g (0 where out_len is -1).  Per frame an entry is extended by
+ * the min(tokens, V - 1) best non-blank acoustic tokens (1 <= tokens <= 65) and by every token that leads to a live prefix.
+ * lm_vocab must equal V.  workspace: av_ctc_beam_lm_workspace_bytes(B, T, V, beam_width, tokens) bytes, 8-byte aligned. */
+int av_ngram_score(const int* ids, const long long* lens, float* out, int B, int Lmax, const float* lm_unigrams, const void* lm_table,
+                   long long lm_slots, int lm_order, int lm_vocab, int lm_bos, int lm_probe_bound, void* stream);
+int av_ctc_beam_lm_workspace_bytes(int B, int T, int V, int beam_width, int tokens, long long* bytes);
+int av_ctc_beam_search_lm(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
+                          int* out_len, float* out_score, float* out_lm_score, void* workspace, long long workspace_bytes, int B, int T,
+                          int V, int blank, int beam_width, int nbest, int tokens, const float* lm_unigrams, const void* lm_table,
+                          long long lm_slots, int lm_order, int lm_vocab, int lm_bos, int lm_probe_bound, float lm_weight,
+                          float token_bonus, void* stream);
 /* CTC loss on the device, opt-in replacement of nn.CTCLoss(blank, zero_infinity=True) (model/trainer.py:25,116-117): the semantics of
  * torch.nn.functional.ctc_loss(..., reduction="none") with padded 2-D targets.  log_probs fp32, element [b][t][v] at
  * b * stride_b + t * stride_t + v (element strides: [B][T][V] and the [T][B][V] view are both taken without a copy); targets int64

@@ -6,7 +6,8 @@ version computes exactly that with one argmax over the whole [T,V] matrix and on
 T*beam_width ``.item()`` calls.
 
 ``prefix_beam_search`` is what the name promises: CTC prefix beam search without a language model (blank-ending and non-blank-ending
-mass per prefix, equal prefixes merged), n-best, on the device kernels of csrc/ctc_beam.hip for GPU tensors and in numpy for host tensors."""
+mass per prefix, equal prefixes merged), n-best, on the device kernels of csrc/ctc_beam.hip for GPU tensors and in numpy for host tensors.
+With ``lm=`` (an lm.NGramLM over token ids) it is the same search with n-gram shallow fusion: csrc/ctc_beam_lm.hip, and the same law in numpy."""
 from __future__ import annotations
 
 import numpy as np
@@ -97,13 +98,82 @@ def _host_prefix_beam(lp: np.ndarray, W: int, blank: int):
     return [list(p) for p in prefixes], [float(x) for x in final]
 
 
-def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False):
-    """CTC prefix beam search without a language model.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
+def _host_prefix_beam_lm(lp: np.ndarray, W: int, blank: int, lm, alpha, beta, tokens: int):
+    """_host_prefix_beam with the fused law of csrc/ctc_beam_lm.hip: an entry also carries g = sum over its tokens of
+    (alpha s(token | tokens before) + beta), every operation rounded to float32 on its own; candidates are ranked by (p_b (+) p_nb) + g;
+    a frame extends by its K = min(tokens, V - 1) best non-blank acoustic tokens plus every extension that lands on a live prefix.
+    -> (id lists, scores, g) of the surviving entries in descending score order."""
+    T, V = lp.shape
+    K = min(tokens, V - 1)
+    NEG = np.float32(-np.inf)
+    alpha, beta = np.float32(alpha), np.float32(beta)
+    cols = np.delete(np.arange(V), blank)
+    order = np.argsort(-lp[:, cols], axis=1, kind="stable")[:, :K]
+    top_t = cols[order]
+    top_v = np.take_along_axis(lp, top_t, axis=1)
+    prefixes, ctx = [()], [lm.start_ctx]
+    pb, pnb, g = np.zeros(1, np.float32), np.full(1, NEG, np.float32), np.zeros(1, np.float32)
+    last = np.full(1, -1)
+    memo = {}
+
+    def s(cx, c):
+        v = memo.get((cx, c))
+        if v is None:
+            v = memo[(cx, c)] = lm.score_ctx(cx, c)
+        return v
+    with np.errstate(invalid="ignore"):
+        for t in range(T):
+            row, n = lp[t], len(prefixes)
+            tot = np.logaddexp(pb, pnb)
+            cand_pb = np.full((n, K + 1), NEG, np.float32)
+            cand_pnb = np.empty((n, K + 1), np.float32)
+            cand_g = np.empty((n, K + 1), np.float32)
+            cand_pb[:, 0] = tot + row[blank]
+            cand_pnb[:, 0] = np.where(last >= 0, pnb + row[np.maximum(last, 0)], NEG)
+            cand_pnb[:, 1:] = np.where(top_t[t][None, :] == last[:, None], pb[:, None], tot[:, None]) + top_v[t][None, :]
+            dead = np.zeros((n, K + 1), bool)
+            dead[:, 1:] = np.isnan(top_v[t])[None, :]
+            cand_g[:, 0] = g
+            for i in range(n):
+                for k in range(K):
+                    cand_g[i, 1 + k] = g[i] + (alpha * s(ctx[i], int(top_t[t, k])) + beta)
+            if n > 1:
+                slot = {p: i for i, p in enumerate(prefixes)}
+                rank = {int(c): r for r, c in enumerate(top_t[t])}
+                for j, p in enumerate(prefixes):
+                    i = slot.get(p[:-1]) if p else None
+                    if i is None:
+                        continue
+                    c = p[-1]                                                  # prefixes[i] + c is prefixes[j]: merge, and drop the duplicate
+                    cand_pnb[j, 0] = np.logaddexp(cand_pnb[j, 0], (pb[i] if last[i] == c else tot[i]) + row[c])
+                    if c in rank:
+                        dead[i, 1 + rank[c]] = True
+            score = (np.logaddexp(cand_pb, cand_pnb) + cand_g).ravel()
+            ids = np.flatnonzero(~dead.ravel())
+            ids = ids[np.argsort(-score[ids], kind="stable")[:W]]
+            src, r = np.divmod(ids, K + 1)
+            prefixes = [prefixes[i] if k == 0 else prefixes[i] + (int(top_t[t, k - 1]),) for i, k in zip(src.tolist(), r.tolist())]
+            ctx = [ctx[i] if k == 0 else lm.push(ctx[i], int(top_t[t, k - 1])) for i, k in zip(src.tolist(), r.tolist())]
+            pb, pnb, g = cand_pb.ravel()[ids], cand_pnb.ravel()[ids], cand_g.ravel()[ids]
+            last = np.where(r == 0, last[src], top_t[t][np.maximum(r - 1, 0)])
+        final = np.logaddexp(pb, pnb) + g
+    return [list(p) for p in prefixes], [float(x) for x in final], [float(x) for x in g]
+
+
+def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False, lm=None, lm_weight=0.5,
+                       token_bonus=0.0, tokens=None):
+    """CTC prefix beam search.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
     B lists of up to ``nbest`` id lists in descending score order (fewer where fewer hypotheses exist); ``return_scores``: (ids, scores)
     with the scores in the same nesting.  ``lengths`` [B]: frames to consume per item (0 gives the empty hypothesis with score 0).
 
     GPU tensor: the two kernels of csrc/ctc_beam.hip (strided views with contiguous rows are taken as they are) and ONE transfer of ids,
-    lengths and scores.  Host tensor: the same law in float32 numpy.  Ties: equal scores are ordered by candidate id (ctc_beam.hip)."""
+    lengths and scores.  Host tensor: the same law in float32 numpy.  Ties: equal scores are ordered by candidate id (ctc_beam.hip).
+
+    ``lm`` = an lm.NGramLM over this vocabulary: shallow fusion (csrc/ctc_beam_lm.hip, av_ctc_beam_search_lm; host tensors: the same law in
+    numpy).  Hypotheses are ranked by acoustic score + g, g = sum over the tokens of (lm_weight * s(token | tokens before) + token_bonus);
+    the returned score is that sum and ``return_scores`` gives (ids, scores, g).  A frame extends an entry by its ``tokens`` best non-blank
+    acoustic tokens (1 <= tokens <= 65, default beam_width + 1) and by every token that leads to a live prefix.  Without ``lm`` the three
+    arguments must keep their defaults."""
     W, nbest, blank = int(beam_width), int(nbest), int(blank)
     if log_probs.dim() == 2:
         log_probs = log_probs[None]
@@ -116,6 +186,20 @@ def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=N
         raise ValueError(f"prefix_beam_search: need V >= 2, 0 <= blank < V and 1 <= T <= 4096, got T={T} V={V} blank={blank}")
     if lengths is not None and (not isinstance(lengths, torch.Tensor) or lengths.numel() != B):
         lengths = torch.as_tensor(lengths, dtype=torch.long).reshape(B)
+    if lm is None:
+        if tokens is not None or lm_weight != 0.5 or token_bonus != 0.0:
+            raise ValueError("prefix_beam_search: lm_weight, token_bonus and tokens need lm=")
+    else:
+        tokens = W + 1 if tokens is None else int(tokens)
+        lm_weight, token_bonus = float(lm_weight), float(token_bonus)
+        if not 1 <= tokens <= 65:
+            raise ValueError(f"prefix_beam_search: tokens {tokens} outside [1, 65]")
+        if lm.vocab_size != V or lm.blank != blank:
+            raise ValueError(f"prefix_beam_search: the language model is over {lm.vocab_size} ids with blank {lm.blank}, the log-probs over "
+                             f"{V} with blank {blank}")
+        if not (np.isfinite(np.float32(lm_weight)) and np.isfinite(np.float32(token_bonus))):
+            raise ValueError(f"prefix_beam_search: lm_weight {lm_weight} and token_bonus {token_bonus} must be finite")
+    lms = None
     if log_probs.is_cuda:
         from . import _lib as L
         from . import ops
@@ -124,28 +208,51 @@ def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=N
             lp = lp.float().contiguous()
         ln = None if lengths is None else lengths.to(device=lp.device, dtype=torch.long).contiguous()
         nbytes = L.ll(0)
-        L.check(L.lib().av_ctc_beam_workspace_bytes(B, T, V, W, L.C.byref(nbytes)), "av_ctc_beam_workspace_bytes")
+        if lm is None:
+            L.check(L.lib().av_ctc_beam_workspace_bytes(B, T, V, W, L.C.byref(nbytes)), "av_ctc_beam_workspace_bytes")
+        else:
+            L.check(L.lib().av_ctc_beam_lm_workspace_bytes(B, T, V, W, tokens, L.C.byref(nbytes)), "av_ctc_beam_lm_workspace_bytes")
         ws = torch.empty((max(1, (nbytes.value + 7) // 8),), dtype=torch.int64, device=lp.device)
-        # one int32 block [B][nbest][T + 2]: ids, then the length, then the score's bits - a single transfer to the host
+        # one int32 block [B][nbest][T + 2 (+ 1)]: ids, then the length, then the bits of the score (and of g) - a single transfer to the host
         out = torch.empty((B, nbest, T), dtype=torch.int32, device=lp.device)
         cnt = torch.empty((B, nbest), dtype=torch.int32, device=lp.device)
         sc = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
-        L.check(L.lib().av_ctc_beam_search(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
-                                           ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, ops.stream()), "av_ctc_beam_search")
-        packed = torch.cat([out, cnt[..., None], sc.view(torch.int32)[..., None]], dim=2).cpu()
+        cols = [out, cnt[..., None], sc.view(torch.int32)[..., None]]
+        if lm is None:
+            L.check(L.lib().av_ctc_beam_search(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
+                                               ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, ops.stream()), "av_ctc_beam_search")
+        else:
+            d = lm.to_device(lp.device)
+            gl = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
+            L.check(L.lib().av_ctc_beam_search_lm(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
+                                                  ops.ptr(gl), ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, tokens,
+                                                  ops.ptr(d.unigrams), ops.ptr(d.table), d.slots, d.order, d.vocab_size, d.bos, d.probe_bound,
+                                                  lm_weight, token_bonus, ops.stream()), "av_ctc_beam_search_lm")
+            cols.append(gl.view(torch.int32)[..., None])
+        packed = torch.cat(cols, dim=2).cpu()
         cnt_h, sc_h = packed[..., T].tolist(), packed[..., T + 1].contiguous().view(torch.float32).tolist()
         ids = [[packed[b, k, :cnt_h[b][k]].tolist() for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
         scores = [[sc_h[b][k] for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
+        if lm is not None:
+            gl_h = packed[..., T + 2].contiguous().view(torch.float32).tolist()
+            lms = [[gl_h[b][k] for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
     else:
         lp_h = log_probs.detach().to(torch.float32).numpy()
         ln_h = [T] * B if lengths is None else [min(max(int(x), 0), T) for x in lengths.tolist()]
-        ids, scores = [], []
+        ids, scores, lms = [], [], (None if lm is None else [])
         for b in range(B):
-            i, s = _host_prefix_beam(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank)
+            if lm is None:
+                i, s = _host_prefix_beam(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank)
+            else:
+                i, s, g = _host_prefix_beam_lm(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank, lm, lm_weight, token_bonus, tokens)
+                lms.append(g[:nbest])
             ids.append(i[:nbest]); scores.append(s[:nbest])
     if nbest == 1:
         ids, scores = [i[0] for i in ids], [s[0] for s in scores]
-    return (ids, scores) if return_scores else ids
+        lms = None if lms is None else [g[0] for g in lms]
+    if not return_scores:
+        return ids
+    return (ids, scores) if lm is None else (ids, scores, lms)
 
 
 def fast_decode(ids, tokenizer):

@@ -23,6 +23,7 @@ from .. import ops
 from .. import _lib as L
 from ..align import forced_align, word_segments
 from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
+from ..lm import NGramLM
 from ..contrastive import contrastive_loss_with_mask
 from ..optim import AvAdam, AvGradScaler
 from ..parallel.dp import GradArena, GradBucketReducer
@@ -75,7 +76,8 @@ class MultimodalTrainer:
     def __init__(self, visual_encoder, audio_encoder, fusion_module, decoder1, tokenizer, learning_rate=1e-4, device="cuda",
                  lambda_=0.1, audio_passes: Optional[int] = None, reducer: Optional[GradBucketReducer] = None, pair_batched: bool = True,
                  visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None,
-                 eval_beam_width: Optional[int] = None):
+                 eval_beam_width: Optional[int] = None, eval_lm=None, eval_lm_weight: Optional[float] = None,
+                 eval_token_bonus: Optional[float] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -100,6 +102,17 @@ class MultimodalTrainer:
         self.eval_beam_width = int(os.environ.get("AVAMD_EVAL_BEAM", "0")) if eval_beam_width is None else int(eval_beam_width)
         if self.eval_beam_width < 0:
             raise ValueError(f"eval_beam_width must be >= 0, got {self.eval_beam_width}")
+        # opt-in: the beam search of evaluate() with n-gram shallow fusion (lm.NGramLM over the tokenizer's ids, csrc/ctc_beam_lm.hip).  eval_lm:
+        # an NGramLM or the path of an ARPA file whose tokens are the tokenizer's pieces; None reads AVAMD_EVAL_LM (default: none),
+        # AVAMD_EVAL_LM_WEIGHT (0.5) and AVAMD_EVAL_TOKEN_BONUS (0.0).  Used only with eval_beam_width > 0
+        eval_lm = os.environ.get("AVAMD_EVAL_LM") or None if eval_lm is None else eval_lm
+        if isinstance(eval_lm, (str, os.PathLike)):
+            eval_lm = NGramLM.from_arpa(os.fspath(eval_lm), tokenizer.token_to_id, vocab_size=tokenizer.vocab_size, blank=tokenizer.blank_id)
+        self.eval_lm = eval_lm
+        self.eval_lm_weight = float(os.environ.get("AVAMD_EVAL_LM_WEIGHT", "0.5")) if eval_lm_weight is None else float(eval_lm_weight)
+        self.eval_token_bonus = float(os.environ.get("AVAMD_EVAL_TOKEN_BONUS", "0.0")) if eval_token_bonus is None else float(eval_token_bonus)
+        if self.eval_lm is not None and self.eval_beam_width == 0:
+            raise ValueError("eval_lm needs eval_beam_width > 0: the greedy decode has no language model")
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.optimizer = AvAdam([
@@ -431,7 +444,10 @@ class MultimodalTrainer:
                 out = self.forward_losses(batch)
                 total_loss += (out["loss1"].item() + out["loss2"].item()) / 2
                 for spk, lp, refs, hyps in (("1", out["log_probs1"], refs1, hyps1), ("2", out["log_probs2"], refs2, hyps2)):
-                    if self.eval_beam_width > 0:
+                    if self.eval_beam_width > 0 and self.eval_lm is not None:
+                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, lm=self.eval_lm,
+                                                 lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
+                    elif self.eval_beam_width > 0:
                         ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id)
                     else:
                         ids = greedy_batch(lp, self.tokenizer.blank_id)   # == simple_beam_search best beam
