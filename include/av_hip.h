@@ -294,7 +294,8 @@ int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b, long long
 int av_ctc_beam_search(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
                        int* out_len, float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V, int blank,
                        int beam_width, int nbest, void* stream);
-/* Token n-gram language model (lm.py: NGramLM) and CTC prefix beam search with its shallow fusion (csrc/ctc_beam_lm.hip).
+/* Token n-gram language model (lm.py: NGramLM) and CTC prefix beam search with its shallow fusion (csrc/ngram_lm.h, csrc/ngram_lm.hip;
+ * the fused search is the other instantiation of the search kernel of csrc/ctc_beam.hip).
  * Tables: lm_unigrams fp32 [lm_vocab + 1][2] = (logp, backoff), natural log, row lm_vocab = begin of sentence; lm_table = lm_slots
  * 16-byte slots {u64 key, f32 logp, f32 backoff}, 16-byte aligned, lm_slots a power of two, key 0 = empty, linear probing from
  * splitmix64(key) & (lm_slots - 1), every stored key within lm_probe_bound probes (lookups make no more, at masked indices); keys = the

@@ -1,6 +1,6 @@
-// CTC prefix beam search on the device, without a language model (the decoder the reference's beam_search.py:2-48 is named after but
-// does not implement; opt-in in evaluate(), model/trainer.py:230,237 of the reference).  float32 in both libraries.
-// The search with an n-gram language model is ctc_beam_lm.hip; what the two share is in ctc_beam_common.h.
+// CTC prefix beam search on the device (the decoder the reference's beam_search.py:2-48 is named after but does not implement; opt-in in
+// evaluate(), model/trainer.py:230,237 of the reference), without a language model and with n-gram shallow fusion: one search kernel,
+// template <bool LM>, instantiated twice.  float32 in both libraries.  The small parts are in ctc_beam_common.h, the n-gram model in ngram_lm.h.
 //
 // Law.  A beam entry is a prefix l with two log-masses: p_b (alignments ending in blank) and p_nb (ending in last(l)); start {(): (0, -inf)}.
 // Per consumed frame, with tot = p_b (+) p_nb and (+) = logaddexp:
@@ -25,7 +25,14 @@
 //
 // Tie rule: equal scores are ordered by candidate id, ascending (a function of the inputs alone: slots are in rank order, ranks of tokens
 // are (value descending, token ascending)).  Everything is deterministic: no floating-point atomics, no order that depends on scheduling.
-#include "ctc_beam_common.h"
+//
+// The fused law (LM = true; the n-gram scores s are those of ngram_lm.h).  An entry also carries g(l) = sum_i (alpha s(l_i | l_<i) + beta),
+// g(()) = 0, and its n-gram context.  Entries are ranked by (p_b (+) p_nb) + g, which is also the returned score; out_lm_score is g.  Stay
+// keeps g; extension by c gives g' = g + (alpha s + beta), every operation rounded on its own, so g is a function of the prefix's content
+// alone, bit for bit, and the two halves of a merge agree on it.  Token pruning is part of this law (with prefix-dependent scores it is not
+// exact any more): a frame extends by its K = min(tokens, V - 1) best non-blank ACOUSTIC tokens plus every c for which l+c is live, merged
+// into that entry's stay; the frame pass runs at width wf = max(tokens - 1, 1).  g' of every candidate is kept in LDS.
+#include "ngram_lm.h"
 
 namespace {
 
@@ -41,8 +48,7 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const float* __rest
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
     if (t >= T) return;
-    int Tb = lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
-    if (t >= Tb) return;
+    if (t >= clamped_length(lengths, b, T)) return;
     const float* row = lp + (long long)b * stride_b + (long long)t * stride_t;
     const bool in_regs = V <= 64 * ROW_REGS;
     float r[ROW_REGS];
@@ -89,33 +95,50 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const float* __rest
 }
 
 // ---- search pass ----
-struct BeamState {
+template <bool LM> struct BeamState {
     float pb[MAXW], pnb[MAXW];
     int last[MAXW], len[MAXW], node[MAXW];
     unsigned long long hash[MAXW];
 };
+template <> struct BeamState<true> : BeamState<false> {
+    float g[MAXW];
+    unsigned long long ctx[MAXW];                   // the n-gram context: the prefix's last N - 1 tokens (ngram_lm.h)
+};
 
+// what only the fused search is given: nothing without a language model
+template <bool LM> struct Fusion {};
+template <> struct Fusion<true> {
+    LmTables lm;
+    unsigned long long ctx0;                        // the empty prefix's context
+    float alpha, beta;
+    float* out_g;
+};
+
+template <bool LM>
 __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ lp, long long stride_b, long long stride_t,
                                                               const long long* __restrict__ lengths, const float* __restrict__ topv,
                                                               const int* __restrict__ topt, int* __restrict__ apar, int* __restrict__ atok,
                                                               int* __restrict__ out_ids, int* __restrict__ out_len,
                                                               float* __restrict__ out_score, int T, int V, int blank, int W, int K, int K1,
-                                                              int nbest) {
-    __shared__ BeamState st[2];
+                                                              int nbest, Fusion<LM> f) {
+    __shared__ BeamState<LM> st[2];
     __shared__ unsigned keys[MAXCAND];
     __shared__ float tot[MAXW], rlast[MAXW], spb[MAXW], spnb[MAXW], tokv[MAXK];
     __shared__ int tokt[MAXK], parent[MAXW], mrank[MAXW], sel[MAXW], hist[256], wsum[4], pick[2], nvalid;
     __shared__ unsigned selkey[MAXW];
     __shared__ float rblank;
+    float* gcand = nullptr;                          // g' of every extension candidate
+    if constexpr (LM) { __shared__ float gc[MAXCAND]; gcand = gc; }
 
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int Tb = lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
+    const int Tb = clamped_length(lengths, b, T);
     const float* base = lp + (long long)b * stride_b;
     const long long tb = (long long)b * T;
     const int C = K + 1;                             // candidates per live entry
 
     if (tid == 0) {
         st[0].pb[0] = 0.f; st[0].pnb[0] = -INFINITY; st[0].last[0] = -1; st[0].len[0] = 0; st[0].node[0] = -1; st[0].hash[0] = 0;
+        if constexpr (LM) { st[0].g[0] = 0.f; st[0].ctx[0] = f.ctx0; }
     }
     int n = 1;
     // the top list of the next frame travels in registers while the current frame is searched
@@ -125,8 +148,8 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
     __syncthreads();
 
     for (int t = 0; t < Tb; ++t) {
-        const BeamState& cur = st[t & 1];
-        BeamState& nxt = st[(t & 1) ^ 1];
+        const BeamState<LM>& cur = st[t & 1];
+        BeamState<LM>& nxt = st[(t & 1) ^ 1];
         const float* row = base + (long long)t * stride_t;
         // 1. this frame's inputs
         if (tid < K) { tokv[tid] = nv; tokt[tid] = nt; }
@@ -151,23 +174,32 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
             }
         }
         __syncthreads();
-        // 3. candidate scores
+        // 3. candidate scores: acoustic, + g with a language model
         const int N = n * C;
         for (int q = tid; q < N; q += 256) {
             const int i = q / C, r = q - i * C;
-            float s;
             if (r == 0) {
                 const float pb = tot[i] + rblank;
                 float pnb = cur.len[i] > 0 ? cur.pnb[i] + rlast[i] : -INFINITY;
                 const int pi = parent[i];
                 if (pi >= 0) pnb = logaddexp_f(pnb, (cur.last[pi] == cur.last[i] ? cur.pb[pi] : tot[pi]) + rlast[i]);
                 spb[i] = pb; spnb[i] = pnb;
-                s = logaddexp_f(pb, pnb);
+                float s = logaddexp_f(pb, pnb);
+                if constexpr (LM) s = __fadd_rn(s, cur.g[i]);
                 keys[q] = key_of(s);
             } else {
                 const int c = tokt[r - 1];
-                s = (c == cur.last[i] ? cur.pb[i] : tot[i]) + tokv[r - 1];
-                keys[q] = c >= 0 ? key_of(s) : 0u;
+                unsigned k = 0u;
+                if (c >= 0) {
+                    float s = (c == cur.last[i] ? cur.pb[i] : tot[i]) + tokv[r - 1];
+                    if constexpr (LM) {
+                        const float gq = __fadd_rn(cur.g[i], __fadd_rn(__fmul_rn(f.alpha, lm_score(f.lm, cur.ctx[i], c)), f.beta));
+                        gcand[q] = gq;
+                        s = __fadd_rn(s, gq);
+                    }
+                    k = key_of(s);
+                }
+                keys[q] = k;
             }
         }
         __syncthreads();
@@ -186,12 +218,18 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
                 if (r == 0) {
                     nxt.pb[rank] = spb[i]; nxt.pnb[rank] = spnb[i]; nxt.last[rank] = cur.last[i]; nxt.len[rank] = cur.len[i];
                     nxt.node[rank] = cur.node[i]; nxt.hash[rank] = cur.hash[i];
+                    if constexpr (LM) { nxt.g[rank] = cur.g[i]; nxt.ctx[rank] = cur.ctx[i]; }
                 } else {
                     const int c = tokt[r - 1];
                     const long long node = (tb + t) * W + rank;
                     apar[node] = cur.node[i]; atok[node] = c;
-                    nxt.pb[rank] = -INFINITY; nxt.pnb[rank] = score_of(k); nxt.last[rank] = c; nxt.len[rank] = cur.len[i] + 1;
+                    nxt.pb[rank] = -INFINITY; nxt.pnb[rank] = (c == cur.last[i] ? cur.pb[i] : tot[i]) + tokv[r - 1];   // as in step 3
+                    nxt.last[rank] = c; nxt.len[rank] = cur.len[i] + 1;
                     nxt.node[rank] = t * W + rank; nxt.hash[rank] = hash_push(cur.hash[i], c);
+                    if constexpr (LM) {
+                        nxt.g[rank] = gcand[q];
+                        nxt.ctx[rank] = ((cur.ctx[i] << 16) | (unsigned long long)(c + 1)) & f.lm.cmask;
+                    }
                 }
             }
         }
@@ -201,14 +239,15 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
     }
 
     // 6. emit: entries are in rank order; walk the back-pointers of the first nbest
-    const BeamState& fin = st[Tb & 1];
+    const BeamState<LM>& fin = st[Tb & 1];
     int* ids = out_ids + (long long)b * nbest * T;
     if (tid < nbest) {
-        int len = -1;                                // fewer than nbest hypotheses exist: length -1, score -inf
-        float score = -INFINITY;
+        int len = -1;                                // fewer than nbest hypotheses exist: length -1, score -inf, lm score 0
+        float score = -INFINITY, g = 0.f;
         if (tid < n) {
             len = fin.len[tid];
             score = logaddexp_f(fin.pb[tid], fin.pnb[tid]);
+            if constexpr (LM) { g = fin.g[tid]; score = __fadd_rn(score, g); }
             int node = fin.node[tid];
             for (int p = len - 1; p >= 0 && node >= 0; --p) {
                 ids[(long long)tid * T + p] = atok[tb * W + node];
@@ -217,6 +256,7 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
         }
         out_len[b * nbest + tid] = len;
         out_score[b * nbest + tid] = score;
+        if constexpr (LM) f.out_g[b * nbest + tid] = g;
         sel[tid] = len;
     }
     __syncthreads();
@@ -226,38 +266,72 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
     }
 }
 
-}  // namespace
-
-extern "C" int av_ctc_beam_workspace_bytes(int B, int T, int V, int beam_width, long long* bytes) {
-    AV_CHECK(bytes, "av_ctc_beam_workspace_bytes: null pointer");
-    AV_CHECK(B >= 0 && T >= 1 && T <= MAXT && V >= 2, "av_ctc_beam_workspace_bytes: bad shape B=%d T=%d V=%d (1 <= T <= %d, V >= 2)", B, T, V, MAXT);
-    AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "av_ctc_beam_workspace_bytes: beam_width %d outside [1, %d]", beam_width, MAXW);
-    *bytes = beam_workspace(B, T, beam_width).total;
-    return AV_OK;
-}
-
-// argument checks shared by the two launching entry points
-static int beam_check(const char* who, const float* log_probs, long long stride_b, long long stride_t, void* workspace,
-                      long long workspace_bytes, int B, int T, int V, int blank, int beam_width) {
+// The argument checks of the launching entry points, in the order in which their errors are reported: beam_check, then the fused search's
+// own arguments, then beam_check_memory.
+static int beam_check(const char* who, const float* log_probs, void* workspace, int B, int T, int V, int blank, int beam_width) {
     AV_CHECK(log_probs && workspace, "%s: null pointer", who);
     AV_CHECK(B >= 0 && B <= 65535 && T >= 1 && T <= MAXT && V >= 2, "%s: bad shape B=%d T=%d V=%d (B <= 65535, 1 <= T <= %d, V >= 2)", who, B,
              T, V, MAXT);
     AV_CHECK(blank >= 0 && blank < V, "%s: blank %d outside [0, %d)", who, blank, V);
     AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "%s: beam_width %d outside [1, %d]", who, beam_width, MAXW);
-    AV_CHECK(stride_t >= V && stride_b >= (long long)T * stride_t, "%s: strides (%lld, %lld) overlap rows of [%d][%d][%d]", who, stride_b,
-             stride_t, B, T, V);
-    const long long need = beam_workspace(B, T, beam_width).total;
+    return AV_OK;
+}
+static int beam_check_memory(const char* who, bool rows, long long stride_b, long long stride_t, long long workspace_bytes, int B, int T,
+                             int V, int beam_width, int wf) {
+    AV_CHECK(!rows || (stride_t >= V && stride_b >= (long long)T * stride_t), "%s: strides (%lld, %lld) overlap rows of [%d][%d][%d]", who,
+             stride_b, stride_t, B, T, V);
+    const long long need = beam_workspace(B, T, beam_width, wf).total;
     AV_CHECK(workspace_bytes >= need, "%s: workspace of %lld bytes is too small, %lld needed", who, workspace_bytes, need);
     return AV_OK;
+}
+
+// the frame pass's width for `tokens` expanded tokens per frame; without a language model the width is W: that is tokens = W + 1
+static int frame_width(int tokens) { return tokens - 1 > 1 ? tokens - 1 : 1; }
+
+// the frame pass at width wf, then the search pass over its top lists (K of the wf + 1 of a row are read); arguments checked by the caller
+template <bool LM>
+static int beam_launch(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids, int* out_len,
+                       float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V, int blank, int beam_width,
+                       int tokens, int nbest, const Fusion<LM>& f, void* stream) {
+    const int wf = frame_width(tokens), K = tokens < V - 1 ? tokens : V - 1;      // tokens > V - 1: every non-blank token is expanded
+    const int rc = av_ctc_beam_frame_pass(log_probs, stride_b, stride_t, lengths, workspace, workspace_bytes, B, T, V, blank, wf, stream);
+    if (rc != AV_OK) return rc;
+    const BeamWorkspace w = beam_workspace(B, T, beam_width, wf);
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(ctc_beam_search_kernel<LM>, dim3(B), dim3(256), 0, (hipStream_t)stream, log_probs, stride_b, stride_t, lengths,
+                       (const float*)(ws + w.topv), (const int*)(ws + w.topt), (int*)(ws + w.apar), (int*)(ws + w.atok), out_ids, out_len,
+                       out_score, T, V, blank, beam_width, K, wf + 1, nbest, f);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+static int workspace_bytes_of(const char* who, int B, int T, int V, int beam_width, int tokens, long long* bytes) {
+    AV_CHECK(bytes, "%s: null pointer", who);
+    AV_CHECK(B >= 0 && T >= 1 && T <= MAXT && V >= 2, "%s: bad shape B=%d T=%d V=%d (1 <= T <= %d, V >= 2)", who, B, T, V, MAXT);
+    AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "%s: beam_width %d outside [1, %d]", who, beam_width, MAXW);
+    AV_CHECK(tokens >= 1 && tokens <= MAXK, "%s: tokens %d outside [1, %d]", who, tokens, MAXK);
+    *bytes = beam_workspace(B, T, beam_width, frame_width(tokens)).total;
+    return AV_OK;
+}
+
+}  // namespace
+
+extern "C" int av_ctc_beam_workspace_bytes(int B, int T, int V, int beam_width, long long* bytes) {
+    return workspace_bytes_of("av_ctc_beam_workspace_bytes", B, T, V, beam_width, beam_width + 1, bytes);
+}
+
+extern "C" int av_ctc_beam_lm_workspace_bytes(int B, int T, int V, int beam_width, int tokens, long long* bytes) {
+    return workspace_bytes_of("av_ctc_beam_lm_workspace_bytes", B, T, V, beam_width, tokens, bytes);
 }
 
 extern "C" int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths,
                                       void* workspace, long long workspace_bytes, int B, int T, int V, int blank, int beam_width,
                                       void* stream) {
-    const int rc = beam_check("av_ctc_beam_frame_pass", log_probs, stride_b, stride_t, workspace, workspace_bytes, B, T, V, blank, beam_width);
-    if (rc != AV_OK) return rc;
-    if (B == 0) return AV_OK;
-    const BeamWorkspace w = beam_workspace(B, T, beam_width);
+    const char* who = "av_ctc_beam_frame_pass";
+    int rc = beam_check(who, log_probs, workspace, B, T, V, blank, beam_width);
+    if (rc == AV_OK) rc = beam_check_memory(who, true, stride_b, stride_t, workspace_bytes, B, T, V, beam_width, beam_width);
+    if (rc != AV_OK || B == 0) return rc;
+    const BeamWorkspace w = beam_workspace(B, T, beam_width, beam_width);
     const int K1 = beam_width + 1, K = K1 < V - 1 ? K1 : V - 1;      // W + 1 > V - 1: every non-blank token is expanded
     char* ws = (char*)workspace;
     hipLaunchKernelGGL(ctc_beam_frame_kernel, dim3((T + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, log_probs, stride_b, stride_t, lengths,
@@ -269,19 +343,38 @@ extern "C" int av_ctc_beam_frame_pass(const float* log_probs, long long stride_b
 extern "C" int av_ctc_beam_search(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
                                   int* out_len, float* out_score, void* workspace, long long workspace_bytes, int B, int T, int V,
                                   int blank, int beam_width, int nbest, void* stream) {
-    AV_CHECK(out_ids && out_len && out_score, "av_ctc_beam_search: null pointer");
-    int rc = beam_check("av_ctc_beam_search", log_probs, stride_b, stride_t, workspace, workspace_bytes, B, T, V, blank, beam_width);
+    const char* who = "av_ctc_beam_search";
+    AV_CHECK(out_ids && out_len && out_score, "%s: null pointer", who);
+    int rc = beam_check(who, log_probs, workspace, B, T, V, blank, beam_width);
+    if (rc == AV_OK) rc = beam_check_memory(who, true, stride_b, stride_t, workspace_bytes, B, T, V, beam_width, beam_width);
     if (rc != AV_OK) return rc;
-    AV_CHECK(nbest >= 1 && nbest <= beam_width, "av_ctc_beam_search: nbest %d outside [1, beam_width %d]", nbest, beam_width);
+    AV_CHECK(nbest >= 1 && nbest <= beam_width, "%s: nbest %d outside [1, beam_width %d]", who, nbest, beam_width);
     if (B == 0) return AV_OK;
-    rc = av_ctc_beam_frame_pass(log_probs, stride_b, stride_t, lengths, workspace, workspace_bytes, B, T, V, blank, beam_width, stream);
+    return beam_launch<false>(log_probs, stride_b, stride_t, lengths, out_ids, out_len, out_score, workspace, workspace_bytes, B, T, V, blank,
+                              beam_width, beam_width + 1, nbest, Fusion<false>{}, stream);
+}
+
+extern "C" int av_ctc_beam_search_lm(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
+                                     int* out_len, float* out_score, float* out_lm_score, void* workspace, long long workspace_bytes, int B,
+                                     int T, int V, int blank, int beam_width, int nbest, int tokens, const float* lm_unigrams,
+                                     const void* lm_table, long long lm_slots, int lm_order, int lm_vocab, int lm_bos, int lm_probe_bound,
+                                     float lm_weight, float token_bonus, void* stream) {
+    const char* who = "av_ctc_beam_search_lm";
+    AV_CHECK(out_ids && out_len && out_score && out_lm_score, "%s: null pointer", who);
+    int rc = beam_check(who, log_probs, workspace, B, T, V, blank, beam_width);
     if (rc != AV_OK) return rc;
-    const BeamWorkspace w = beam_workspace(B, T, beam_width);
-    const int K1 = beam_width + 1, K = K1 < V - 1 ? K1 : V - 1;
-    char* ws = (char*)workspace;
-    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, log_probs, stride_b, stride_t, lengths,
-                       (const float*)(ws + w.topv), (const int*)(ws + w.topt), (int*)(ws + w.apar), (int*)(ws + w.atok), out_ids, out_len,
-                       out_score, T, V, blank, beam_width, K, K1, nbest);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    AV_CHECK(nbest >= 1 && nbest <= beam_width, "%s: nbest %d outside [1, beam_width %d]", who, nbest, beam_width);
+    AV_CHECK(tokens >= 1 && tokens <= MAXK, "%s: tokens %d outside [1, %d]", who, tokens, MAXK);
+    AV_CHECK(lm_vocab == V, "%s: the language model's vocabulary %d is not V = %d", who, lm_vocab, V);
+    AV_CHECK(lm_weight == lm_weight && token_bonus == token_bonus && fabsf(lm_weight) <= 3.0e38f && fabsf(token_bonus) <= 3.0e38f,
+             "%s: lm_weight and token_bonus must be finite", who);
+    Fusion<true> f;
+    rc = lm_check(who, lm_unigrams, lm_table, lm_slots, lm_order, lm_vocab, lm_bos, lm_probe_bound, &f.lm);
+    // rows = false: the strides are left to the frame pass, which reports them after the workspace and not at all for B = 0
+    if (rc == AV_OK) rc = beam_check_memory(who, false, stride_b, stride_t, workspace_bytes, B, T, V, beam_width, frame_width(tokens));
+    if (rc != AV_OK || B == 0) return rc;
+    f.ctx0 = lm_bos >= 0 ? ((unsigned long long)(lm_bos + 1) & f.lm.cmask) : 0ull;
+    f.alpha = lm_weight; f.beta = token_bonus; f.out_g = out_lm_score;
+    return beam_launch<true>(log_probs, stride_b, stride_t, lengths, out_ids, out_len, out_score, workspace, workspace_bytes, B, T, V, blank,
+                             beam_width, tokens, nbest, f, stream);
 }

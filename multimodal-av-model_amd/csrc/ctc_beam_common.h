@@ -1,5 +1,6 @@
-// What the two CTC prefix beam searches share (ctc_beam.hip: no language model; ctc_beam_lm.hip: n-gram shallow fusion): the limits, the
-// log-sum, the order-preserving key of a score, the content hash of a prefix and the workgroup scan.  Moved here unchanged from ctc_beam.hip.
+// The small parts of the CTC prefix beam search (ctc_beam.hip) that are not the search itself: the limits, the workspace layout, the
+// length clamp, the log-sum, the order-preserving key of a score, the 64-bit mixer (also the n-gram table's hash, ngram_lm.h), the content
+// hash of a prefix, the workgroup scan and the radix select.
 #pragma once
 #include "av_common.h"
 
@@ -11,14 +12,21 @@ constexpr int MAXK = MAXW + 1;
 constexpr int MAXCAND = MAXW * (MAXK + 1);          // W (W + 2)
 
 struct BeamWorkspace {
-    long long topv, topt, apar, atok, total;        // byte offsets: top values fp32 [B][T][W+1], top tokens int32 [B][T][W+1], arena int32 [B][T][W] x 2
+    long long topv, topt, apar, atok, total;        // byte offsets: top values fp32 [B][T][wf+1], top tokens int32 [B][T][wf+1], arena int32 [B][T][W] x 2
 };
 
-static BeamWorkspace beam_workspace(long long B, long long T, long long W) {
+// wf is the width of the frame pass that fills the top lists: W without a language model, max(tokens - 1, 1) with one.  The arena is sized
+// for the larger of W and wf, so that the frame pass at width wf accepts the same workspace.
+static BeamWorkspace beam_workspace(long long B, long long T, long long W, long long wf) {
     BeamWorkspace w;
-    const long long top = B * T * (W + 1) * 4, arena = B * T * W * 4;
-    w.topv = 0; w.topt = top; w.apar = 2 * top; w.atok = 2 * top + arena; w.total = 2 * top + 2 * arena;
+    const long long top = B * T * (wf + 1) * 4, arena = B * T * W * 4;
+    w.topv = 0; w.topt = top; w.apar = 2 * top; w.atok = 2 * top + arena; w.total = 2 * top + 2 * B * T * (W > wf ? W : wf) * 4;
     return w;
+}
+
+// frames (or tokens) of item b that are consumed: lengths[b] clamped to [0, T], T without lengths
+__device__ __forceinline__ int clamped_length(const long long* lengths, int b, int T) {
+    return lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
 }
 
 __device__ __forceinline__ float logaddexp_f(float a, float b) {
@@ -32,14 +40,16 @@ __device__ __forceinline__ unsigned key_of(float x) {
     const unsigned u = __float_as_uint(x);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ __forceinline__ float score_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-__device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) {
-    unsigned long long z = h + 0x9E3779B97F4A7C15ull * (unsigned long long)(c + 1);
+// splitmix64: the finaliser, a bijection of the 64-bit integers, and the increment its generator adds before it
+constexpr unsigned long long MIX64_STEP = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+
+__device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) { return mix64(h + MIX64_STEP * (unsigned long long)(c + 1)); }
 
 // inclusive prefix sum of one int per thread over the 256 threads of the workgroup (wsum: 4 ints of LDS); ends with the data visible
 __device__ __forceinline__ int block_scan_incl(int v, int* wsum) {
@@ -56,7 +66,7 @@ __device__ __forceinline__ int block_scan_incl(int v, int* wsum) {
     return v;
 }
 
-// Step 4 of both searches.  The want = min(W, N) largest of keys[0 .. N): the want-th largest key by a 4 x 8-bit radix select (LDS histogram
+// Step 4 of the search.  The want = min(W, N) largest of keys[0 .. N): the want-th largest key by a 4 x 8-bit radix select (LDS histogram
 // and one workgroup scan per pass), then every key above it and the first equal ones in candidate order into sel[] / selkey[] (in no order
 // among themselves); called by all 256 threads, ends with the selection visible.  hist: 256 ints, wsum: 4, pick: 2, sel / selkey: MAXW.
 __device__ __forceinline__ int beam_select(const unsigned* keys, int N, int W, int* hist, int* wsum, int* pick, int* sel, unsigned* selkey) {

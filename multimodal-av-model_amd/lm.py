@@ -1,4 +1,4 @@
-"""Token n-gram language model for shallow fusion in CTC prefix beam search (beam_search.prefix_beam_search(lm=...), csrc/ctc_beam_lm.hip).
+"""Token n-gram language model for shallow fusion in CTC prefix beam search (beam_search.prefix_beam_search(lm=...), csrc/ngram_lm.h, csrc/ctc_beam.hip).
 
 ``NGramLM`` is a backoff n-gram model over TOKEN IDS - the tokenizer's pieces, not words - of order 1 <= N <= 4 over a vocabulary of
 V <= 65533 ids.  Every n-gram stores ``logp`` and ``backoff``, natural log, float32.  An optional begin-of-sentence id ``bos = V`` is never
@@ -6,7 +6,7 @@ predicted; it is only ever the oldest context token of the empty prefix.  End of
 an ARPA file is read, so a hypothesis pays nothing for ending.  A token without a unigram scores ``unk_logp`` (the file's ``<unk>`` if it
 has one, else -10 ln 10, pyctcdecode's default), so every score is finite.
 
-The scoring law (one wording for this file, csrc/ctc_beam_lm.hip and DESIGN §0.0d).  s(c | ctx), for m from min(N - 1, tokens available)
+The scoring law (one wording for this file, csrc/ngram_lm.h and DESIGN §0.0d).  s(c | ctx), for m from min(N - 1, tokens available)
 down to 1: look up the (m + 1)-gram "last m context tokens, c"; found: return acc + logp.  Not found: acc += backoff(the m-gram that is
 the context), then drop the context's oldest token; a context that is absent adds nothing.  At m = 0 return acc + unigram(c).  acc starts
 at 0; the additions are float32, in that order, and there is nothing else - no multiply, no libm - so the host and the device give the same

@@ -265,6 +265,23 @@ def test_abi_argument_errors_in_both_libraries():
         assert lib.av_ngram_score(P, None, P, 0, 5, P, P, 16, 3, V, -1, 4, None) == 0                     # B = 0: nothing to do
 
 
+def test_workspace_sizes_are_the_closed_forms_in_both_libraries():
+    """One layout for both searches: top lists of the frame pass at width wf, then the arena sized for max(W, wf); wf = W without a
+    language model, max(tokens - 1, 1) with one (below, equal to and above W)."""
+    for lib in _libs():
+        for B in (0, 3):
+            for T in (1, 37):
+                for W in (1, 8, 64):
+                    got = ctypes.c_longlong(-1)
+                    assert lib.av_ctc_beam_workspace_bytes(B, T, 50, W, ctypes.byref(got)) == 0
+                    assert got.value == 8 * B * T * (W + 1) + 8 * B * T * W, (B, T, W, got.value)
+                    for tokens in (1, 2, 9, 40, 65):
+                        wf = max(tokens - 1, 1)
+                        got = ctypes.c_longlong(-1)
+                        assert lib.av_ctc_beam_lm_workspace_bytes(B, T, 50, W, tokens, ctypes.byref(got)) == 0
+                        assert got.value == 8 * B * T * (wf + 1) + 8 * B * T * max(W, wf), (B, T, W, tokens, got.value)
+
+
 def _trainer(**kw):
     init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
     tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")

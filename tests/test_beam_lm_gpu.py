@@ -1,5 +1,5 @@
 """GPU: the n-gram tables on the device (av_ngram_score against NGramLM.score, bit for bit) and CTC prefix beam search with shallow fusion
-(csrc/ctc_beam_lm.hip, beam_search.prefix_beam_search(lm=...)) in both libraries: against the fused float64 law of tests/lm_ref.py under the
+(csrc/ctc_beam.hip, beam_search.prefix_beam_search(lm=...)) in both libraries: against the fused float64 law of tests/lm_ref.py under the
 agreement rule of tests/beam_ref.py, against av_ctc_beam_search at zero weights, against the package's host path, for determinism and
 output padding, and as the opt-in decoder of MultimodalTrainer.evaluate()."""
 import numpy as np
