@@ -354,6 +354,33 @@ int av_ctc_align(const float* log_probs, long long stride_b, long long stride_t,
                  const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
                  int* out_state, int* out_span, float* out_token_score, float* out_score, void* workspace, long long workspace_bytes,
                  void* stream);
+/* Word, character and token error counts on the device: edit distance with operation counts between ONE reference and N hypotheses per
+ * utterance, from token ids through a device copy of the tokenizer's piece table - what MultimodalTrainer.evaluate() measures
+ * (word_error_rate of model/trainer.py, the jiwer.wer stand-in), plus the character and token levels and the S / D / I breakdown.
+ * ref_ids int32 [B][ref_ld] (Lr used), ref_lens int64 [B]; hyp_ids int32, element [b][n][i] at b * hyp_ld_b + n * hyp_ld_n + i (Lh used:
+ * the out_ids block of av_ctc_beam_search is taken as it is), hyp_lens int64 [B][N], < 0 = absent hypothesis (that kernel's out_len).
+ * Ids and lengths are read from DEVICE memory (no host copy, no synchronisation); lengths are clamped to [0, L]; ids at or past a
+ * sequence's length are never read.  0 <= Lr, Lh <= 4096 (ids may be NULL where L = 0).
+ * Text of a sequence (csrc/error_counts.hip): ids outside [0, V) and ids equal to the sequence's skip id (ref_skip_id / hyp_skip_id; < 0:
+ * none) are dropped; the code points of the remaining pieces - piece i = piece_chars[piece_offsets[i] .. piece_offsets[i + 1]), offsets
+ * int32 [V + 1] non-decreasing, at most max_piece code points per piece (longer ones are cut there) - are concatenated, U+2581 read as
+ * U+0020, and leading / trailing U+0020 stripped.  Level 0 (token): the kept ids.  Level 1 (character): the stripped text, inner spaces
+ * included.  Level 2 (word): maximal runs of non-space code points, equal when their code points are equal (a hash filters, the content
+ * decides).  piece_offsets = piece_chars = NULL: levels 1 and 2 are -1, V and max_piece are ignored and the ids are compared as given
+ * (only the skip id is dropped): the entry for callers that bring their own symbols.
+ * Counts of a pair: among all alignments (match, substitution, deletion of a reference symbol, insertion of a hypothesis symbol) the
+ * lexicographically smallest (S + D + I, S, D) - minimum edits, then fewest substitutions, then fewest deletions: a property of the pair.
+ * out_counts int32 [B][N][3][4]: level x (S, D, I, R = reference length at that level); hits = R - S - D, hypothesis length = R - D + I.
+ * All four are -1 at every level of an absent hypothesis, and at levels 1 and 2 of a pair one of whose texts exceeds 4096 code points
+ * before the strip (its level 0 is still computed).  Every element is written.
+ * workspace: av_error_counts_workspace_bytes(B, N, Lr, Lh, max_piece) bytes (max_piece = 0: no table), 16-byte aligned; a smaller one is
+ * an error status.  Two launches (expansion: one workgroup per sequence; distance: one wave per pair and level, at most 48 KiB of LDS).
+ * Deterministic: no atomics, integers only. */
+int av_error_counts_workspace_bytes(int B, int N, int Lr, int Lh, int max_piece, long long* bytes);
+int av_error_counts(const int* ref_ids, long long ref_ld, const long long* ref_lens, const int* hyp_ids, long long hyp_ld_b,
+                    long long hyp_ld_n, const long long* hyp_lens, int B, int N, int Lr, int Lh, int ref_skip_id, int hyp_skip_id,
+                    const int* piece_offsets, const int* piece_chars, int V, int max_piece, int* out_counts, void* workspace,
+                    long long workspace_bytes, void* stream);
 /* device side of the input pipeline (dataset/multi_speaker_dataset.py:13-59; decoding wav / npy files stays on the host):
  * av_lip_gray_resize: src [T][Hs][Ws][C] (uint8 if src_is_u8 else fp32) -> dst fp32 [T][Hd][Wd] = bilinear(mean over C) / divisor
  *   (:49-58: .astype(float32).mean(-1), cv2.resize INTER_LINEAR law, / 255), float32 operation order of the reference;

@@ -77,7 +77,7 @@ class MultimodalTrainer:
                  lambda_=0.1, audio_passes: Optional[int] = None, reducer: Optional[GradBucketReducer] = None, pair_batched: bool = True,
                  visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None,
                  eval_beam_width: Optional[int] = None, eval_lm=None, eval_lm_weight: Optional[float] = None,
-                 eval_token_bonus: Optional[float] = None):
+                 eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -113,6 +113,11 @@ class MultimodalTrainer:
         self.eval_token_bonus = float(os.environ.get("AVAMD_EVAL_TOKEN_BONUS", "0.0")) if eval_token_bonus is None else float(eval_token_bonus)
         if self.eval_lm is not None and self.eval_beam_width == 0:
             raise ValueError("eval_lm needs eval_beam_width > 0: the greedy decode has no language model")
+        # opt-in: evaluate() also counts token / character / word errors with their S / D / I split on the device (error_rate.error_counts,
+        # csrc/error_counts.hip), leaves the rates in ``last_report`` and takes its WER from those counts.  None reads AVAMD_EVAL_REPORT
+        # (default "0"); off: none of that code runs
+        self.eval_report = os.environ.get("AVAMD_EVAL_REPORT", "0") == "1" if eval_report is None else bool(eval_report)
+        self.last_report = None
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.optimizer = AvAdam([
@@ -439,6 +444,8 @@ class MultimodalTrainer:
         refs1, hyps1, refs2, hyps2 = [], [], [], []
         total_loss = 0.0
         lam, self.lambda_ = self.lambda_, 0.0
+        self.last_report = None
+        report = self._report_begin() if self.eval_report else None
         try:
             for batch in dataloader:
                 out = self.forward_losses(batch)
@@ -455,16 +462,42 @@ class MultimodalTrainer:
                     for i, seq in enumerate(ids):
                         hyps.append(fast_decode(seq, self.tokenizer))
                         refs.append(self.tokenizer.decode(txt[i][: int(tl[i])].tolist()))
+                    if report is not None:
+                        self._report_add(report, spk, txt, tl, ids)
             if self.native_ctc:
                 self.fusion_module.drain_flag_check()
         finally:
             self.lambda_ = lam
-        wer1, wer2 = word_error_rate(refs1, hyps1), word_error_rate(refs2, hyps2)
+        if report is not None:
+            wer1, wer2 = self._report_finish(report)
+        else:
+            wer1, wer2 = word_error_rate(refs1, hyps1), word_error_rate(refs2, hyps2)
         avg_wer = (wer1 + wer2) / 2
         avg_loss = total_loss / max(1, len(dataloader))
         print(f"[Eval] WER1: {wer1:.3f}, WER2: {wer2:.3f}, Avg: {avg_wer:.3f}, Loss: {avg_loss:.4f}")
         self.last_decoded = (hyps1, hyps2)
         return avg_loss, avg_wer
+
+    # evaluate()'s opt-in report: error counts of both speakers on the device, one accumulator, one transfer after the loop
+    def _report_begin(self):
+        from ..error_rate import PieceTable
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("MultimodalTrainer.evaluate: eval_report counts errors on the GPU; there is no CPU fallback")
+        return {"table": PieceTable.from_tokenizer(self.tokenizer), "acc": torch.zeros((2, 3, 4), dtype=torch.int64, device=self.device)}
+
+    def _report_add(self, report, spk, txt, tl, ids):
+        from ..error_rate import error_counts
+        # references as evaluate() decodes them (nothing skipped), hypotheses as fast_decode does (the blank skipped)
+        counts = error_counts(txt.to(self.device, non_blocking=True), ids, ref_lengths=tl, table=report["table"], ref_skip=-1,
+                              hyp_skip=self.tokenizer.blank_id)
+        best = counts[:, 0].long()
+        report["acc"][int(spk) - 1] += (best * (best[:, :, 3:4] >= 0)).sum(0)          # a level of -1 (a text beyond the limit) adds nothing
+
+    def _report_finish(self, report):
+        from ..error_rate import rates
+        acc = report["acc"].cpu()
+        self.last_report = {"speaker1": rates(acc[0]), "speaker2": rates(acc[1])}
+        return self.last_report["speaker1"]["word"]["rate"], self.last_report["speaker2"]["word"]["rate"]
 
     @torch.no_grad()
     def align(self, batch, frame_rate: float = 25.0):
