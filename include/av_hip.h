@@ -319,6 +319,36 @@ int av_ctc_beam_search_lm(const float* log_probs, long long stride_b, long long 
                           int V, int blank, int beam_width, int nbest, int tokens, const float* lm_unigrams, const void* lm_table,
                           long long lm_slots, int lm_order, int lm_vocab, int lm_bos, int lm_probe_bound, float lm_weight,
                           float token_bonus, void* stream);
+/* Contextual phrase biasing (bias.py: ContextBias; csrc/context_bias.h, csrc/context_bias.hip; the biased search is the third
+ * instantiation of the search kernel of csrc/ctc_beam.hip).
+ * Law: P = a set of distinct phrases of 1..32 token ids in [0, V), none the blank.  The state of a prefix is (k, tail), (0, ()) for the
+ * empty one; per token c: tail <- the longest suffix of tail + (c) that is a prefix of some phrase (possibly empty); if tail is in P,
+ * k <- k + |tail| and tail <- ().  m = k + |tail| (k banked, |tail| refundable).
+ * Tables: the trie of P, node 0 = root.  bias_nodes int32 [bias_node_count][2] = (failure link = the deepest node that spells a proper
+ * suffix of the node's path, depth | terminal << 16), 8-byte aligned; bias_edges = bias_slots 16-byte slots {u64 key, i32 child, i32 0},
+ * 16-byte aligned, bias_slots a power of two, key 0 = empty, key = (node << 16) | (token + 1), linear probing from
+ * splitmix64(key) & (bias_slots - 1), every stored key within bias_probe_bound probes (lookups make no more, at masked indices).
+ * 2 <= V <= 65533.  Node indices read from the tables are clamped to [0, bias_node_count): a corrupt table gives wrong counts only.
+ * av_context_bias_count: ids int32 [B][Lmax], lens optional int64 [B] on the device (clamped to [0, Lmax]); out int32 [B][Lmax][2],
+ * 8-byte aligned, = (k, |tail|) after each token, 0 past the length; an id outside [0, V) or equal to the blank matches nothing and
+ * resets the tail.  One thread per sequence.
+ * av_ctc_beam_search_bias: the arguments and outputs of av_ctc_beam_search_lm; the language model is optional (lm_unigrams = lm_table
+ * = NULL and lm_order = 0: none, no lookups, g_lm = +0, the other lm_ arguments are ignored).  An entry also carries (node, k);
+ * g = g_lm (+) (bias_weight (x) float(m)), one multiply and one add rounded to fp32 each, g_lm = the g of av_ctc_beam_search_lm, and
+ * entries are ranked by (p_b (+) p_nb) + g during the search.  Token pruning is av_ctc_beam_search_lm's: biasing re-ranks the
+ * min(tokens, V - 1) best acoustic tokens and the live extensions, it injects no token.  After the last consumed frame
+ * g_fin = g_lm (+) (bias_weight (x) float(k)) and the surviving entries are ranked again by (p_b (+) p_nb) + g_fin (descending, ties
+ * to the earlier rank); that is out_score, out_lm_score = g_lm, out_bias_count int32 [B][nbest] = k (0 where out_len is -1).
+ * bias_weight: fp32, finite, nats per matched token, may be negative.  workspace: av_ctc_beam_lm_workspace_bytes(B, T, V, beam_width,
+ * tokens) bytes, 8-byte aligned. */
+int av_context_bias_count(const int* ids, const long long* lens, int* out, int B, int Lmax, int V, int blank, const void* bias_nodes,
+                          const void* bias_edges, int bias_node_count, long long bias_slots, int bias_probe_bound, void* stream);
+int av_ctc_beam_search_bias(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int* out_ids,
+                            int* out_len, float* out_score, float* out_lm_score, int* out_bias_count, void* workspace,
+                            long long workspace_bytes, int B, int T, int V, int blank, int beam_width, int nbest, int tokens,
+                            const float* lm_unigrams, const void* lm_table, long long lm_slots, int lm_order, int lm_vocab, int lm_bos,
+                            int lm_probe_bound, float lm_weight, float token_bonus, const void* bias_nodes, const void* bias_edges,
+                            int bias_node_count, long long bias_slots, int bias_probe_bound, float bias_weight, void* stream);
 /* CTC loss on the device, opt-in replacement of nn.CTCLoss(blank, zero_infinity=True) (model/trainer.py:25,116-117): the semantics of
  * torch.nn.functional.ctc_loss(..., reduction="none") with padded 2-D targets.  log_probs fp32, element [b][t][v] at
  * b * stride_b + t * stride_t + v (element strides: [B][T][V] and the [T][B][V] view are both taken without a copy); targets int64

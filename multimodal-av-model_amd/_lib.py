@@ -133,6 +133,9 @@ SIGNATURES = {
     "av_ngram_score": [vp, vp, vp, i32, i32, vp, vp, ll, i32, i32, i32, i32, vp],
     "av_ctc_beam_lm_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(ll)],
     "av_ctc_beam_search_lm": [vp, ll, ll, vp, vp, vp, vp, vp, vp, ll, i32, i32, i32, i32, i32, i32, i32, vp, vp, ll, i32, i32, i32, i32, f32, f32, vp],
+    "av_context_bias_count": [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, ll, i32, vp],
+    "av_ctc_beam_search_bias": [vp, ll, ll, vp, vp, vp, vp, vp, vp, vp, ll, i32, i32, i32, i32, i32, i32, i32, vp, vp, ll, i32, i32, i32, i32, f32,
+                                f32, vp, vp, i32, ll, i32, f32, vp],
     "av_ctc_loss_fwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "av_ctc_loss_bwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "av_ctc_align_workspace_bytes": [i32, i32, i32, C.POINTER(ll)],

@@ -8,7 +8,8 @@ T*beam_width ``.item()`` calls.
 ``prefix_beam_search`` is what the name promises: CTC prefix beam search without a language model (blank-ending and non-blank-ending
 mass per prefix, equal prefixes merged), n-best, on the device kernels of csrc/ctc_beam.hip for GPU tensors and in numpy for host tensors.
 With ``lm=`` (an lm.NGramLM over token ids) it is the same search with n-gram shallow fusion: the same kernel's other instantiation, and the
-same function in numpy."""
+same function in numpy.  With ``bias=`` (a bias.ContextBias: phrases that are likely in this recording) it is the same search with contextual
+phrase biasing, with or without ``lm``: the kernel's third instantiation, and again the same function in numpy."""
 from __future__ import annotations
 
 import functools
@@ -53,16 +54,20 @@ def greedy_batch(log_probs: torch.Tensor, blank: int, lengths: torch.Tensor = No
     return res
 
 
-def _host_prefix_beam(lp: np.ndarray, W: int, blank: int, lm=None, alpha=0.0, beta=0.0, tokens=None):
-    """One utterance, float32 [T, V] -> (id lists, scores, g or None) of the surviving entries in descending score order.  The law and the
+def _host_prefix_beam(lp: np.ndarray, W: int, blank: int, lm=None, alpha=0.0, beta=0.0, tokens=None, bias=None, w=0.0):
+    """One utterance, float32 [T, V] -> (id lists, scores, g or None, k or None) of the surviving entries in descending score order.  The law and the
     order of csrc/ctc_beam.hip: per frame only the K best non-blank tokens (value descending, token ascending) are expanded, plus every
     extension that lands on a live prefix (compared by content), which is merged into that prefix's stay; candidate slot * (K + 1) + r
     (r = 0: stay, r >= 1: token of rank r - 1) is ranked by score, equal scores by candidate id.  Without ``lm`` K = min(W + 1, V - 1) and
     the score is p_b (+) p_nb.  With ``lm`` K = min(tokens, V - 1), an entry also carries g = sum over its tokens of
     (alpha s(token | tokens before) + beta), every operation rounded to float32 on its own, and the score is (p_b (+) p_nb) + g.  There is
-    no g arithmetic at all without ``lm``: adding a zero would turn a score of -0.0 into +0.0."""
+    no g arithmetic at all without ``lm``: adding a zero would turn a score of -0.0 into +0.0.  With ``bias`` (with or without ``lm``;
+    K = min(tokens, V - 1)) g above is g_lm, +0 throughout without ``lm``; an entry also carries the phrase automaton's state (node, k),
+    it is ranked by (p_b (+) p_nb) + (g_lm + w * float32(k + |tail|)), and after the last frame the entries are ranked again (stable) by
+    (p_b (+) p_nb) + (g_lm + w * float32(k)), which is the returned score (bias.py: the law)."""
     T, V = lp.shape
-    K = min(W + 1 if lm is None else tokens, V - 1)
+    fused = lm is not None or bias is not None
+    K = min(tokens if fused else W + 1, V - 1)
     NEG = np.float32(-np.inf)
     cols = np.delete(np.arange(V), blank)
     order = np.argsort(-lp[:, cols], axis=1, kind="stable")[:, :K]           # stable: equal values keep the smaller token first
@@ -71,9 +76,14 @@ def _host_prefix_beam(lp: np.ndarray, W: int, blank: int, lm=None, alpha=0.0, be
     prefixes = [()]
     pb, pnb = np.zeros(1, np.float32), np.full(1, NEG, np.float32)
     last = np.full(1, -1)
+    if fused:
+        g = np.zeros(1, np.float32)
     if lm is not None:
         alpha, beta = np.float32(alpha), np.float32(beta)
-        ctx, g, s = [lm.start_ctx], np.zeros(1, np.float32), functools.lru_cache(None)(lm.score_ctx)
+        ctx, s = [lm.start_ctx], functools.lru_cache(None)(lm.score_ctx)
+    if bias is not None:
+        w, state, depth = np.float32(w), [(0, 0)], bias.depth
+        step = functools.lru_cache(None)(bias.step)
     with np.errstate(invalid="ignore"):
         for t in range(T):
             row, n = lp[t], len(prefixes)
@@ -97,31 +107,50 @@ def _host_prefix_beam(lp: np.ndarray, W: int, blank: int, lm=None, alpha=0.0, be
                     if c in rank:
                         dead[i, 1 + rank[c]] = True
             score = np.logaddexp(cand_pb, cand_pnb)
-            if lm is not None:
+            if fused:
                 cand_g = np.empty((n, K + 1), np.float32)
                 cand_g[:, 0] = g
                 for i in range(n):
                     for k in range(K):
-                        cand_g[i, 1 + k] = g[i] + (alpha * s(ctx[i], int(top_t[t, k])) + beta)
-                score = score + cand_g
+                        cand_g[i, 1 + k] = g[i] if lm is None else g[i] + (alpha * s(ctx[i], int(top_t[t, k])) + beta)
+                if bias is None:
+                    score = score + cand_g
+                else:
+                    m = np.empty((n, K + 1), np.float32)
+                    for i, (node, kb) in enumerate(state):
+                        m[i, 0] = kb + depth[node]
+                        for k in range(K):
+                            nd, kk = step(node, kb, int(top_t[t, k]))
+                            m[i, 1 + k] = kk + depth[nd]
+                    score = score + (cand_g + w * m)
             ids = np.flatnonzero(~dead.ravel())
             ids = ids[np.argsort(-score.ravel()[ids], kind="stable")[:W]]
             src, r = np.divmod(ids, K + 1)
             prefixes = [prefixes[i] if k == 0 else prefixes[i] + (int(top_t[t, k - 1]),) for i, k in zip(src.tolist(), r.tolist())]
             if lm is not None:
                 ctx = [ctx[i] if k == 0 else lm.push(ctx[i], int(top_t[t, k - 1])) for i, k in zip(src.tolist(), r.tolist())]
+            if bias is not None:
+                state = [state[i] if k == 0 else step(*state[i], int(top_t[t, k - 1])) for i, k in zip(src.tolist(), r.tolist())]
+            if fused:
                 g = cand_g.ravel()[ids]
             pb, pnb = cand_pb.ravel()[ids], cand_pnb.ravel()[ids]
             last = np.where(r == 0, last[src], top_t[t][np.maximum(r - 1, 0)])
         final = np.logaddexp(pb, pnb)
-        if lm is not None:
+        if bias is not None:
+            kb = np.array([k for _, k in state], np.int64)
+            final = final + (g + w * kb.astype(np.float32))
+            order = np.argsort(-final, kind="stable")
+            prefixes, final, g, kb = [prefixes[i] for i in order], final[order], g[order], kb[order]
+        elif lm is not None:
             final = final + g
-    return [list(p) for p in prefixes], [float(x) for x in final], (None if lm is None else [float(x) for x in g])
+    return ([list(p) for p in prefixes], [float(x) for x in final], (None if not fused else [float(x) for x in g]),
+            (None if bias is None else [int(x) for x in kb]))
 
 
-def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens):
-    """[B, T, V] on the GPU -> per utterance the lists of ids, of scores and (with ``lm``, else None) of g of its hypotheses.  The kernels of
-    csrc/ctc_beam.hip and ONE transfer: an int32 block [B][nbest][T + 2 (+ 1)] of ids, then the length, then the bits of the score (and of g)."""
+def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias=None, bias_weight=0.0):
+    """[B, T, V] on the GPU -> per utterance the lists of ids, of scores, (with ``lm`` or ``bias``, else None) of g and (with ``bias``, else
+    None) of the banked phrase counts of its hypotheses.  The kernels of csrc/ctc_beam.hip and ONE transfer: an int32 block
+    [B][nbest][T + 2 (+ 1) (+ 1)] of ids, then the length, then the bits of the score (and of g, and the count)."""
     from . import _lib as L
     from . import ops
     B, T, V = log_probs.shape
@@ -130,7 +159,7 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
         lp = lp.float().contiguous()
     ln = None if lengths is None else lengths.to(device=lp.device, dtype=torch.long).contiguous()
     nbytes = L.ll(0)
-    if lm is None:
+    if lm is None and bias is None:
         L.check(L.lib().av_ctc_beam_workspace_bytes(B, T, V, W, L.C.byref(nbytes)), "av_ctc_beam_workspace_bytes")
     else:
         L.check(L.lib().av_ctc_beam_lm_workspace_bytes(B, T, V, W, tokens, L.C.byref(nbytes)), "av_ctc_beam_lm_workspace_bytes")
@@ -139,7 +168,18 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
     cnt = torch.empty((B, nbest), dtype=torch.int32, device=lp.device)
     sc = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
     cols = [out, cnt[..., None], sc.view(torch.int32)[..., None]]
-    if lm is None:
+    if bias is not None:
+        d, db = (None if lm is None else lm.to_device(lp.device)), bias.to_device(lp.device)
+        gl = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
+        kb = torch.empty((B, nbest), dtype=torch.int32, device=lp.device)
+        lm_args = (None, None, 0, 0, 0, -1, 0, 0.0, 0.0) if d is None else (ops.ptr(d.unigrams), ops.ptr(d.table), d.slots, d.order,
+                                                                            d.vocab_size, d.bos, d.probe_bound, lm_weight, token_bonus)
+        L.check(L.lib().av_ctc_beam_search_bias(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
+                                                ops.ptr(gl), ops.ptr(kb), ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, tokens,
+                                                *lm_args, ops.ptr(db.nodes), ops.ptr(db.edges), db.node_count, db.slots, db.probe_bound,
+                                                bias_weight, ops.stream()), "av_ctc_beam_search_bias")
+        cols += [gl.view(torch.int32)[..., None], kb[..., None]]
+    elif lm is None:
         L.check(L.lib().av_ctc_beam_search(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
                                            ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, ops.stream()), "av_ctc_beam_search")
     else:
@@ -157,11 +197,12 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
         x = packed[..., col].contiguous().view(torch.float32).tolist()
         return [[x[b][k] for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
     ids = [[packed[b, k, :cnt_h[b][k]].tolist() for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
-    return ids, floats(T + 1), (None if lm is None else floats(T + 2))
+    counts = None if bias is None else [[packed[b, k, T + 3].item() for k in range(nbest) if cnt_h[b][k] >= 0] for b in range(B)]
+    return ids, floats(T + 1), (None if lm is None and bias is None else floats(T + 2)), counts
 
 
 def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False, lm=None, lm_weight=0.5,
-                       token_bonus=0.0, tokens=None):
+                       token_bonus=0.0, tokens=None, bias=None, bias_weight=1.0):
     """CTC prefix beam search.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
     B lists of up to ``nbest`` id lists in descending score order (fewer where fewer hypotheses exist); ``return_scores``: (ids, scores)
     with the scores in the same nesting.  ``lengths`` [B]: frames to consume per item (0 gives the empty hypothesis with score 0).
@@ -173,7 +214,16 @@ def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=N
     tensors: the same law in numpy).  Hypotheses are ranked by acoustic score + g, g = sum over the tokens of
     (lm_weight * s(token | tokens before) + token_bonus); the returned score is that sum and ``return_scores`` gives (ids, scores, g).  A
     frame extends an entry by its ``tokens`` best non-blank acoustic tokens (1 <= tokens <= 65, default beam_width + 1) and by every token
-    that leads to a live prefix.  Without ``lm`` the three arguments must keep their defaults."""
+    that leads to a live prefix.  Without ``lm`` lm_weight and token_bonus must keep their defaults, and so must ``tokens`` unless ``bias`` is given.
+
+    ``bias`` = a bias.ContextBias over this vocabulary: contextual phrase biasing, with or without ``lm`` (the kernel's third
+    instantiation, av_ctc_beam_search_bias; host tensors: the same law in numpy).  During the search a hypothesis is also credited
+    ``bias_weight`` (float32 nats, finite, may be negative) for every token of a completed phrase and of a running partial match; after the
+    last frame the credit of a partial match is taken back and the hypotheses are ranked again (the law: bias.py).  The returned score is
+    acoustic score + g + bias_weight * count and ``return_scores`` gives (ids, scores, g, counts): g as above (zeros without ``lm``),
+    counts = the tokens of completed phrases per hypothesis.  Biasing re-ranks among the ``tokens`` acoustically best tokens of a frame
+    (and the live extensions); it does not inject tokens: raise ``tokens`` (<= 65) to let weaker phrase continuations in.  Without
+    ``bias``, bias_weight must keep its default."""
     W, nbest, blank = int(beam_width), int(nbest), int(blank)
     if log_probs.dim() == 2:
         log_probs = log_probs[None]
@@ -186,32 +236,46 @@ def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=N
         raise ValueError(f"prefix_beam_search: need V >= 2, 0 <= blank < V and 1 <= T <= 4096, got T={T} V={V} blank={blank}")
     if lengths is not None and (not isinstance(lengths, torch.Tensor) or lengths.numel() != B):
         lengths = torch.as_tensor(lengths, dtype=torch.long).reshape(B)
-    if lm is None:
-        if tokens is not None or lm_weight != 0.5 or token_bonus != 0.0:
-            raise ValueError("prefix_beam_search: lm_weight, token_bonus and tokens need lm=")
-    else:
+    if bias is None and bias_weight != 1.0:
+        raise ValueError("prefix_beam_search: bias_weight needs bias=")
+    if lm is None and (lm_weight != 0.5 or token_bonus != 0.0 or (tokens is not None and bias is None)):
+        raise ValueError("prefix_beam_search: lm_weight, token_bonus and tokens need lm=")
+    if lm is not None or bias is not None:
         tokens = W + 1 if tokens is None else int(tokens)
-        lm_weight, token_bonus = float(lm_weight), float(token_bonus)
         if not 1 <= tokens <= 65:
             raise ValueError(f"prefix_beam_search: tokens {tokens} outside [1, 65]")
+    if bias is not None:
+        bias_weight = float(bias_weight)
+        if bias.vocab_size != V or bias.blank != blank:
+            raise ValueError(f"prefix_beam_search: the phrases are over {bias.vocab_size} ids with blank {bias.blank}, the log-probs over "
+                             f"{V} with blank {blank}")
+        if not abs(bias_weight) <= float(np.finfo(np.float32).max):          # NaN, an infinity, or one once it is a float32
+            raise ValueError(f"prefix_beam_search: bias_weight {bias_weight} must be finite")
+    if lm is not None:
+        lm_weight, token_bonus = float(lm_weight), float(token_bonus)
         if lm.vocab_size != V or lm.blank != blank:
             raise ValueError(f"prefix_beam_search: the language model is over {lm.vocab_size} ids with blank {lm.blank}, the log-probs over "
                              f"{V} with blank {blank}")
         if not (np.isfinite(np.float32(lm_weight)) and np.isfinite(np.float32(token_bonus))):
             raise ValueError(f"prefix_beam_search: lm_weight {lm_weight} and token_bonus {token_bonus} must be finite")
     if log_probs.is_cuda:
-        ids, scores, lms = _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens)
+        ids, scores, lms, counts = _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
     else:
         lp_h = log_probs.detach().to(torch.float32).numpy()
         ln_h = [T] * B if lengths is None else [min(max(int(x), 0), T) for x in lengths.tolist()]
-        found = [_host_prefix_beam(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank, lm, lm_weight, token_bonus, tokens) for b in range(B)]
-        ids, scores = [i[:nbest] for i, _, _ in found], [s[:nbest] for _, s, _ in found]
-        lms = None if lm is None else [g[:nbest] for _, _, g in found]
+        found = [_host_prefix_beam(np.ascontiguousarray(lp_h[b, :ln_h[b]]), W, blank, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
+                 for b in range(B)]
+        ids, scores = [f[0][:nbest] for f in found], [f[1][:nbest] for f in found]
+        lms = None if lm is None and bias is None else [f[2][:nbest] for f in found]
+        counts = None if bias is None else [f[3][:nbest] for f in found]
     if nbest == 1:
         ids, scores = [i[0] for i in ids], [s[0] for s in scores]
         lms = None if lms is None else [g[0] for g in lms]
+        counts = None if counts is None else [k[0] for k in counts]
     if not return_scores:
         return ids
+    if bias is not None:
+        return ids, scores, lms, counts
     return (ids, scores) if lm is None else (ids, scores, lms)
 
 

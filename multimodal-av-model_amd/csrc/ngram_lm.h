@@ -24,16 +24,26 @@ struct LmTables {
     int order, V, probe;
 };
 
-__device__ __forceinline__ bool lm_find(const LmTables& lm, unsigned long long key, float& logp, float& backoff) {
-    unsigned long long i = mix64(key + MIX64_STEP) & lm.smask;                 // splitmix64(key)
-    for (int p = 0; p < lm.probe; ++p) {
-        const uint4 s = lm.tab[i];
+// One lookup in a table of this contract (also the phrase automaton's edge table, context_bias.h): the two value words of the slot that
+// holds `key`, in at most `probe` probes at masked indices.
+__device__ __forceinline__ bool slot_find(const uint4* tab, unsigned long long smask, int probe, unsigned long long key, unsigned& v0,
+                                          unsigned& v1) {
+    unsigned long long i = mix64(key + MIX64_STEP) & smask;                    // splitmix64(key)
+    for (int p = 0; p < probe; ++p) {
+        const uint4 s = tab[i];
         const unsigned long long k = (unsigned long long)s.x | ((unsigned long long)s.y << 32);
-        if (k == key) { logp = __uint_as_float(s.z); backoff = __uint_as_float(s.w); return true; }
+        if (k == key) { v0 = s.z; v1 = s.w; return true; }
         if (k == 0ull) return false;
-        i = (i + 1) & lm.smask;
+        i = (i + 1) & smask;
     }
     return false;
+}
+
+__device__ __forceinline__ bool lm_find(const LmTables& lm, unsigned long long key, float& logp, float& backoff) {
+    unsigned z, w;
+    if (!slot_find(lm.tab, lm.smask, lm.probe, key, z, w)) return false;
+    logp = __uint_as_float(z); backoff = __uint_as_float(w);
+    return true;
 }
 
 // s(c | ctx); 0 <= c < V

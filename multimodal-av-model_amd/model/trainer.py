@@ -23,6 +23,7 @@ from .. import ops
 from .. import _lib as L
 from ..align import forced_align, word_segments
 from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
+from ..bias import ContextBias
 from ..lm import NGramLM
 from ..contrastive import contrastive_loss_with_mask
 from ..optim import AvAdam, AvGradScaler
@@ -77,7 +78,8 @@ class MultimodalTrainer:
                  lambda_=0.1, audio_passes: Optional[int] = None, reducer: Optional[GradBucketReducer] = None, pair_batched: bool = True,
                  visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None,
                  eval_beam_width: Optional[int] = None, eval_lm=None, eval_lm_weight: Optional[float] = None,
-                 eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None):
+                 eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None, eval_bias=None,
+                 eval_bias_weight: Optional[float] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -113,6 +115,16 @@ class MultimodalTrainer:
         self.eval_token_bonus = float(os.environ.get("AVAMD_EVAL_TOKEN_BONUS", "0.0")) if eval_token_bonus is None else float(eval_token_bonus)
         if self.eval_lm is not None and self.eval_beam_width == 0:
             raise ValueError("eval_lm needs eval_beam_width > 0: the greedy decode has no language model")
+        # opt-in: the beam search of evaluate() with contextual phrase biasing (bias.ContextBias over the tokenizer's ids), with or without
+        # eval_lm.  eval_bias: a ContextBias or the path of a phrase file (UTF-8, one phrase per line); None reads AVAMD_EVAL_BIAS (default:
+        # none) and AVAMD_EVAL_BIAS_WEIGHT (1.0: a setting, not a tuned value).  Used only with eval_beam_width > 0; unset: none of that code runs
+        eval_bias = os.environ.get("AVAMD_EVAL_BIAS") or None if eval_bias is None else eval_bias
+        if isinstance(eval_bias, (str, os.PathLike)):
+            eval_bias = ContextBias.from_file(os.fspath(eval_bias), tokenizer)
+        self.eval_bias = eval_bias
+        self.eval_bias_weight = float(os.environ.get("AVAMD_EVAL_BIAS_WEIGHT", "1.0")) if eval_bias_weight is None else float(eval_bias_weight)
+        if self.eval_bias is not None and self.eval_beam_width == 0:
+            raise ValueError("eval_bias needs eval_beam_width > 0: the greedy decode has no phrase biasing")
         # opt-in: evaluate() also counts token / character / word errors with their S / D / I split on the device (error_rate.error_counts,
         # csrc/error_counts.hip), leaves the rates in ``last_report`` and takes its WER from those counts.  None reads AVAMD_EVAL_REPORT
         # (default "0"); off: none of that code runs
@@ -451,7 +463,12 @@ class MultimodalTrainer:
                 out = self.forward_losses(batch)
                 total_loss += (out["loss1"].item() + out["loss2"].item()) / 2
                 for spk, lp, refs, hyps in (("1", out["log_probs1"], refs1, hyps1), ("2", out["log_probs2"], refs2, hyps2)):
-                    if self.eval_beam_width > 0 and self.eval_lm is not None:
+                    if self.eval_beam_width > 0 and self.eval_bias is not None:
+                        fusion = {} if self.eval_lm is None else dict(lm=self.eval_lm, lm_weight=self.eval_lm_weight,
+                                                                      token_bonus=self.eval_token_bonus)
+                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, bias=self.eval_bias,
+                                                 bias_weight=self.eval_bias_weight, **fusion)
+                    elif self.eval_beam_width > 0 and self.eval_lm is not None:
                         ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, lm=self.eval_lm,
                                                  lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
                     elif self.eval_beam_width > 0:

@@ -1,6 +1,6 @@
 """CTC prefix beam search with n-gram shallow fusion on one MI355X: device events around av_ctc_beam_search_lm at B 64, T 199, V 800, W 8
 for tokens K = 9 and K = 32 and two trigram tables (a small one that fits L2 and one of tens of MB), in alternation with
-av_ctc_beam_search at the same shape (both are instantiations of one kernel, csrc/ctc_beam.hip: template <bool LM>)
+av_ctc_beam_search at the same shape (both are instantiations of one kernel, csrc/ctc_beam.hip: template <int F>)
 and next to the package's host path.  20 repeats after 3 warm-ups, median and range, profiler off.  There is no gate: the file records
 the ratio and the per-frame cost.  Writes profiles/ctc_beam_lm_timing.txt.
 
