@@ -365,6 +365,31 @@ int av_ctc_loss_fwd(const float* log_probs, long long stride_b, long long stride
 int av_ctc_loss_bwd(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
                     const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
                     const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll, float* grad, void* stream);
+/* N-best form of the CTC loss, for minimum word error rate training (mwer.py): the negative log-likelihood and the gradient of N label
+ * sequences per utterance against ONE shared [T][V] block of log-probs, which is read once and whose gradient is written once.
+ * log_probs and the strides are as for av_ctc_loss_fwd; hyp_ids int32, element [b][n][i] at b * hyp_ld_b + n * hyp_ld_n + i (the out_ids
+ * block of av_ctc_beam_search is taken as it is), hyp_lens int64 [B][N] (as for av_error_counts), input_lengths int64 [B]: one T_b per
+ * utterance, shared by its N hypotheses, clamped to [0, T].  Lmax = (S_max - 1) / 2.  Everything is read from DEVICE memory.
+ * A present hypothesis is exactly an item of av_ctc_loss_fwd with zero_infinity = 0 (the same kernel: bit-identical nll).  An item is OUT
+ * when hyp_lens < 0 (absent), hyp_lens > Lmax (NOT clamped: a cut hypothesis is a different hypothesis), an id is outside [0, V) or no
+ * path exists; ids at or past a length are never read.
+ * av_ctc_nbest_fwd: nll fp32 [B][N], +inf for an out item; log_alpha / log_beta = workspaces fp32 [B][N][T][S_max] for the gradient
+ * (log_beta NULL: values only, log_alpha may then be NULL too).
+ * av_ctc_nbest_bwd: grad fp32 [B][T][V] contiguous = G_b exp(log_probs) - sum_n grad_nll[b][n] occupancy_{b,n} for t < T_b, the sum over
+ * the items that are not out in ascending n and G_b = sum_n grad_nll[b][n] in the same order; exactly 0 for t >= T_b and for every row
+ * of an utterance whose items are all out; every element is written.  grad_nll of an out item is never read into any sum (an inf or
+ * NaN there cannot reach grad).
+ * Limits: 1 <= N <= 64, 1 <= B <= 65535 (the gradient's grid y; the lattice launches 2 B N workgroups), T, V >= 1, 0 <= blank < V, S_max
+ * odd, hyp_ld_n >= Lmax, hyp_ld_b >= (N - 1) hyp_ld_n + Lmax; LDS: that of av_ctc_loss_fwd for the forward, W (V + S_max) floats plus
+ * 3 N Lmax + 3 N ints for the gradient (W = 4, 2 or 1 wavefronts), both within 64 KiB - otherwise an error status.
+ * Deterministic: no floating-point atomics (bit-identical results for identical inputs). */
+int av_ctc_nbest_fwd(const float* log_probs, long long stride_b, long long stride_t, const int* hyp_ids, long long hyp_ld_b,
+                     long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V, int S_max,
+                     int blank, float* nll, float* log_alpha, float* log_beta, void* stream);
+int av_ctc_nbest_bwd(const float* log_probs, long long stride_b, long long stride_t, const int* hyp_ids, long long hyp_ld_b,
+                     long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V, int S_max,
+                     int blank, const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll, float* grad,
+                     void* stream);
 /* CTC forced alignment on the device: the best frame path (Viterbi) of each transcript through the CTC lattice of the log-probs and
  * lengths the trainer hands to its loss and decoder (model/trainer.py:116-117, 229-242), for word timestamps and alignment scores.
  * log_probs, strides, targets, target_ld, lengths, the clamping of T_b / L_b and odd S_max = 2 Lmax + 1 are as for av_ctc_loss_fwd

@@ -138,6 +138,8 @@ SIGNATURES = {
                                 f32, vp, vp, i32, ll, i32, f32, vp],
     "av_ctc_loss_fwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "av_ctc_loss_bwd": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "av_ctc_nbest_fwd": [vp, ll, ll, vp, ll, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "av_ctc_nbest_bwd": [vp, ll, ll, vp, ll, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "av_ctc_align_workspace_bytes": [i32, i32, i32, C.POINTER(ll)],
     "av_ctc_align": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, ll, vp],
     "av_error_counts_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(ll)],

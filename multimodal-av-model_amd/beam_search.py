@@ -147,17 +147,17 @@ def _host_prefix_beam(lp: np.ndarray, W: int, blank: int, lm=None, alpha=0.0, be
             (None if bias is None else [int(x) for x in kb]))
 
 
-def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias=None, bias_weight=0.0):
-    """[B, T, V] on the GPU -> per utterance the lists of ids, of scores, (with ``lm`` or ``bias``, else None) of g and (with ``bias``, else
-    None) of the banked phrase counts of its hypotheses.  The kernels of csrc/ctc_beam.hip and ONE transfer: an int32 block
-    [B][nbest][T + 2 (+ 1) (+ 1)] of ids, then the length, then the bits of the score (and of g, and the count)."""
+def _device_beam_launch(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias=None, bias_weight=0.0):
+    """[B, T, V] on the GPU -> the device tensors the kernels of csrc/ctc_beam.hip wrote, and no transfer: ids int32 [B, nbest, T], lengths
+    int32 [B, nbest] (< 0: absent), scores fp32 [B, nbest], g fp32 [B, nbest] (with ``lm`` or ``bias``, else None) and the banked phrase
+    counts int32 [B, nbest] (with ``bias``, else None)."""
     from . import _lib as L
     from . import ops
     B, T, V = log_probs.shape
     lp = log_probs.detach()
     if lp.dtype != torch.float32 or lp.stride(2) != 1 or lp.stride(1) < V or lp.stride(0) < T * lp.stride(1):
         lp = lp.float().contiguous()
-    ln = None if lengths is None else lengths.to(device=lp.device, dtype=torch.long).contiguous()
+    ln = None if lengths is None else lengths.to(device=lp.device, dtype=torch.long, non_blocking=True).contiguous()
     nbytes = L.ll(0)
     if lm is None and bias is None:
         L.check(L.lib().av_ctc_beam_workspace_bytes(B, T, V, W, L.C.byref(nbytes)), "av_ctc_beam_workspace_bytes")
@@ -167,7 +167,7 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
     out = torch.empty((B, nbest, T), dtype=torch.int32, device=lp.device)
     cnt = torch.empty((B, nbest), dtype=torch.int32, device=lp.device)
     sc = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
-    cols = [out, cnt[..., None], sc.view(torch.int32)[..., None]]
+    gl = kb = None
     if bias is not None:
         d, db = (None if lm is None else lm.to_device(lp.device)), bias.to_device(lp.device)
         gl = torch.empty((B, nbest), dtype=torch.float32, device=lp.device)
@@ -178,7 +178,6 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
                                                 ops.ptr(gl), ops.ptr(kb), ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, tokens,
                                                 *lm_args, ops.ptr(db.nodes), ops.ptr(db.edges), db.node_count, db.slots, db.probe_bound,
                                                 bias_weight, ops.stream()), "av_ctc_beam_search_bias")
-        cols += [gl.view(torch.int32)[..., None], kb[..., None]]
     elif lm is None:
         L.check(L.lib().av_ctc_beam_search(ops.ptr(lp), lp.stride(0), lp.stride(1), ops.ptr(ln), ops.ptr(out), ops.ptr(cnt), ops.ptr(sc),
                                            ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, ops.stream()), "av_ctc_beam_search")
@@ -189,7 +188,20 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
                                               ops.ptr(gl), ops.ptr(ws), ws.numel() * 8, B, T, V, blank, W, nbest, tokens,
                                               ops.ptr(d.unigrams), ops.ptr(d.table), d.slots, d.order, d.vocab_size, d.bos, d.probe_bound,
                                               lm_weight, token_bonus, ops.stream()), "av_ctc_beam_search_lm")
+    return out, cnt, sc, gl, kb
+
+
+def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias=None, bias_weight=0.0):
+    """[B, T, V] on the GPU -> per utterance the lists of ids, of scores, (with ``lm`` or ``bias``, else None) of g and (with ``bias``, else
+    None) of the banked phrase counts of its hypotheses.  The launches of ``_device_beam_launch`` and ONE transfer: an int32 block
+    [B][nbest][T + 2 (+ 1) (+ 1)] of ids, then the length, then the bits of the score (and of g, and the count)."""
+    B, T, V = log_probs.shape
+    out, cnt, sc, gl, kb = _device_beam_launch(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
+    cols = [out, cnt[..., None], sc.view(torch.int32)[..., None]]
+    if gl is not None:
         cols.append(gl.view(torch.int32)[..., None])
+    if kb is not None:
+        cols.append(kb[..., None])
     packed = torch.cat(cols, dim=2).cpu()
     cnt_h = packed[..., T].tolist()
 
@@ -201,29 +213,8 @@ def _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, toke
     return ids, floats(T + 1), (None if lm is None and bias is None else floats(T + 2)), counts
 
 
-def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False, lm=None, lm_weight=0.5,
-                       token_bonus=0.0, tokens=None, bias=None, bias_weight=1.0):
-    """CTC prefix beam search.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
-    B lists of up to ``nbest`` id lists in descending score order (fewer where fewer hypotheses exist); ``return_scores``: (ids, scores)
-    with the scores in the same nesting.  ``lengths`` [B]: frames to consume per item (0 gives the empty hypothesis with score 0).
-
-    GPU tensor: the two kernels of csrc/ctc_beam.hip (strided views with contiguous rows are taken as they are) and ONE transfer of ids,
-    lengths and scores.  Host tensor: the same law in float32 numpy.  Ties: equal scores are ordered by candidate id (ctc_beam.hip).
-
-    ``lm`` = an lm.NGramLM over this vocabulary: shallow fusion (the search kernel's other instantiation, av_ctc_beam_search_lm; host
-    tensors: the same law in numpy).  Hypotheses are ranked by acoustic score + g, g = sum over the tokens of
-    (lm_weight * s(token | tokens before) + token_bonus); the returned score is that sum and ``return_scores`` gives (ids, scores, g).  A
-    frame extends an entry by its ``tokens`` best non-blank acoustic tokens (1 <= tokens <= 65, default beam_width + 1) and by every token
-    that leads to a live prefix.  Without ``lm`` lm_weight and token_bonus must keep their defaults, and so must ``tokens`` unless ``bias`` is given.
-
-    ``bias`` = a bias.ContextBias over this vocabulary: contextual phrase biasing, with or without ``lm`` (the kernel's third
-    instantiation, av_ctc_beam_search_bias; host tensors: the same law in numpy).  During the search a hypothesis is also credited
-    ``bias_weight`` (float32 nats, finite, may be negative) for every token of a completed phrase and of a running partial match; after the
-    last frame the credit of a partial match is taken back and the hypotheses are ranked again (the law: bias.py).  The returned score is
-    acoustic score + g + bias_weight * count and ``return_scores`` gives (ids, scores, g, counts): g as above (zeros without ``lm``),
-    counts = the tokens of completed phrases per hypothesis.  Biasing re-ranks among the ``tokens`` acoustically best tokens of a frame
-    (and the live extensions); it does not inject tokens: raise ``tokens`` (<= 65) to let weaker phrase continuations in.  Without
-    ``bias``, bias_weight must keep its default."""
+def _beam_args(log_probs, beam_width, blank, lengths, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight):
+    """The validation ``prefix_beam_search`` and ``nbest_on_device`` share -> the normalised arguments."""
     W, nbest, blank = int(beam_width), int(nbest), int(blank)
     if log_probs.dim() == 2:
         log_probs = log_probs[None]
@@ -258,6 +249,52 @@ def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=N
                              f"{V} with blank {blank}")
         if not (np.isfinite(np.float32(lm_weight)) and np.isfinite(np.float32(token_bonus))):
             raise ValueError(f"prefix_beam_search: lm_weight {lm_weight} and token_bonus {token_bonus} must be finite")
+    return log_probs, lengths, W, blank, nbest, lm_weight, token_bonus, tokens, bias_weight
+
+
+def nbest_on_device(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, lm=None, lm_weight=0.5, token_bonus=0.0, tokens=None,
+                    bias=None, bias_weight=1.0):
+    """``prefix_beam_search`` on a GPU tensor without its transfer: the same arguments and validation, the same kernels, and the result
+    stays on the device - nothing is copied to the host and nothing synchronises.  -> (ids int32 [B, nbest, T], lens int32 [B, nbest],
+    scores fp32 [B, nbest]), with ``lm`` also g fp32 [B, nbest], with ``bias`` g (zeros without ``lm``) and the phrase counts int32
+    [B, nbest].  Row n of an utterance is its n-th best hypothesis; lens < 0 marks an absent one (fewer than ``nbest`` exist), ids at or
+    past a length are unspecified.  This is the block ``error_rate.error_counts`` and ``ops.ctc_nbest_nll`` take as it is."""
+    if not isinstance(log_probs, torch.Tensor) or not log_probs.is_cuda:
+        raise RuntimeError("nbest_on_device: log_probs must be on the GPU; there is no CPU fallback (prefix_beam_search decodes host tensors)")
+    log_probs, lengths, W, blank, nbest, lm_weight, token_bonus, tokens, bias_weight = _beam_args(
+        log_probs, beam_width, blank, lengths, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
+    out, cnt, sc, gl, kb = _device_beam_launch(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
+    if bias is not None:
+        return out, cnt, sc, gl, kb
+    return (out, cnt, sc) if lm is None else (out, cnt, sc, gl)
+
+
+def prefix_beam_search(log_probs: torch.Tensor, beam_width=5, blank=0, lengths=None, nbest=1, return_scores=False, lm=None, lm_weight=0.5,
+                       token_bonus=0.0, tokens=None, bias=None, bias_weight=1.0):
+    """CTC prefix beam search.  [B,T,V] (or [T,V] = one utterance) -> list of B id lists; ``nbest`` > 1: list of
+    B lists of up to ``nbest`` id lists in descending score order (fewer where fewer hypotheses exist); ``return_scores``: (ids, scores)
+    with the scores in the same nesting.  ``lengths`` [B]: frames to consume per item (0 gives the empty hypothesis with score 0).
+
+    GPU tensor: the two kernels of csrc/ctc_beam.hip (strided views with contiguous rows are taken as they are) and ONE transfer of ids,
+    lengths and scores.  Host tensor: the same law in float32 numpy.  Ties: equal scores are ordered by candidate id (ctc_beam.hip).
+
+    ``lm`` = an lm.NGramLM over this vocabulary: shallow fusion (the search kernel's other instantiation, av_ctc_beam_search_lm; host
+    tensors: the same law in numpy).  Hypotheses are ranked by acoustic score + g, g = sum over the tokens of
+    (lm_weight * s(token | tokens before) + token_bonus); the returned score is that sum and ``return_scores`` gives (ids, scores, g).  A
+    frame extends an entry by its ``tokens`` best non-blank acoustic tokens (1 <= tokens <= 65, default beam_width + 1) and by every token
+    that leads to a live prefix.  Without ``lm`` lm_weight and token_bonus must keep their defaults, and so must ``tokens`` unless ``bias`` is given.
+
+    ``bias`` = a bias.ContextBias over this vocabulary: contextual phrase biasing, with or without ``lm`` (the kernel's third
+    instantiation, av_ctc_beam_search_bias; host tensors: the same law in numpy).  During the search a hypothesis is also credited
+    ``bias_weight`` (float32 nats, finite, may be negative) for every token of a completed phrase and of a running partial match; after the
+    last frame the credit of a partial match is taken back and the hypotheses are ranked again (the law: bias.py).  The returned score is
+    acoustic score + g + bias_weight * count and ``return_scores`` gives (ids, scores, g, counts): g as above (zeros without ``lm``),
+    counts = the tokens of completed phrases per hypothesis.  Biasing re-ranks among the ``tokens`` acoustically best tokens of a frame
+    (and the live extensions); it does not inject tokens: raise ``tokens`` (<= 65) to let weaker phrase continuations in.  Without
+    ``bias``, bias_weight must keep its default."""
+    log_probs, lengths, W, blank, nbest, lm_weight, token_bonus, tokens, bias_weight = _beam_args(
+        log_probs, beam_width, blank, lengths, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
+    B, T, V = log_probs.shape
     if log_probs.is_cuda:
         ids, scores, lms, counts = _device_prefix_beam(log_probs, lengths, W, blank, nbest, lm, lm_weight, token_bonus, tokens, bias, bias_weight)
     else:

@@ -16,6 +16,16 @@
 // position order; the blank states are summed per lane in position order and combined by a fixed butterfly.
 // Out-of-range data cannot cause out-of-bounds accesses: T_b is clamped to [0, T], L_b to [0, Lmax], and an utterance with a label
 // outside [0, V) is infeasible (every emission -inf => nll = +inf, zero gradient).
+//
+// N-best form (av_ctc_nbest_fwd / _bwd: minimum word error rate training, mwer.py): N label sequences per utterance against ONE [T, V] block
+// of log-probs.  The forward is the SAME lattice kernel, instantiated with items = B N (item b N + n reads utterance b's rows and T_b, int32
+// labels at b ld_b + n ld_n): a present hypothesis is bit for bit an item of av_ctc_loss_fwd.  An item is OUT (nll = +inf, no gradient, its
+// grad_nll never read) when its length is < 0 (absent) or > Lmax (not clamped: a cut hypothesis is another hypothesis), when an id is
+// outside [0, V) or when no path exists.
+//   ctc_nbest_grad_kernel  the shape of ctc_grad_kernel, one wavefront per [b, t] row that loops over the N hypotheses in ascending n: the
+//                          label chains of all N hypotheses are built once per workgroup, g_n occ_n is accumulated into the LDS row in
+//                          hypothesis order (each class has one owner lane per hypothesis: no atomics), the log-prob row is read once and
+//                          grad = G_b exp(lp) - sum_n g_n occ_n, G_b = sum_n g_n over the items that are not out, is written once.
 #include "av_common.h"
 
 namespace {
@@ -32,11 +42,14 @@ __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
     return logf(expf(a - m) + expf(b - m) + expf(c - m)) + m;
 }
 
+// NBEST = false: the items are the B utterances, labels int64 [B][ld_b] (av_ctc_loss_fwd).  NBEST = true: items = B N, item b N + n reads
+// the log-probs and T_b of utterance b and the int32 labels at b ld_b + n ld_n; a length < 0 or > Lmax makes it out (never clamped).
+template <bool NBEST>
 __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restrict__ lp, long long stride_b, long long stride_t,
-                                                          const long long* __restrict__ targets, long long target_ld,
+                                                          const void* __restrict__ labels, long long ld_b, long long ld_n,
                                                           const long long* __restrict__ input_lengths,
-                                                          const long long* __restrict__ target_lengths, int B, int T, int V, int S_max,
-                                                          int blank, int zero_infinity, float* __restrict__ nll,
+                                                          const long long* __restrict__ label_lengths, int items, int N, int T, int V,
+                                                          int S_max, int blank, int zero_infinity, float* __restrict__ nll,
                                                           float* __restrict__ log_alpha, float* __restrict__ log_beta) {
     extern __shared__ float smem[];
     float* rowA = smem;                                   // [S_max] lattice row t-1 / t (ping-pong)
@@ -46,17 +59,22 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
     int* skip = lab + S_max;                              // [S_max] 1 = the transition from two states back exists
     __shared__ int bad;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const bool mirror = blockIdx.x >= B;                  // beta: the alpha recursion with time and states reversed
-    const int b = mirror ? blockIdx.x - B : blockIdx.x;
+    const bool mirror = blockIdx.x >= items;              // beta: the alpha recursion with time and states reversed
+    const int item = mirror ? blockIdx.x - items : blockIdx.x;
+    const int b = NBEST ? item / N : item;                // the utterance whose log-probs and T_b the item reads
     const int Tb = ctc_clamp_len(input_lengths[b], T);
-    const int Lb = ctc_clamp_len(target_lengths[b], (S_max - 1) / 2);
+    const long long Lraw = label_lengths[item];
+    const bool out_len = NBEST && (Lraw < 0 || Lraw > (S_max - 1) / 2);
+    const int Lb = out_len ? 0 : ctc_clamp_len(Lraw, (S_max - 1) / 2);
     const int S = 2 * Lb + 1;
     float* out = mirror ? log_beta : log_alpha;
-    if (tid == 0) bad = 0;
+    const long long lab0 = NBEST ? (long long)b * ld_b + (long long)(item - b * N) * ld_n : (long long)item * ld_b;
+    if (tid == 0) bad = out_len ? 1 : 0;
     __syncthreads();
     for (int s = tid; s < S; s += nt) {
         const int so = mirror ? S - 1 - s : s;            // state of the original lattice
-        long long c = (so & 1) ? targets[(long long)b * target_ld + (so >> 1)] : (long long)blank;
+        long long c = blank;
+        if (so & 1) c = NBEST ? (long long)((const int*)labels)[lab0 + (so >> 1)] : ((const long long*)labels)[lab0 + (so >> 1)];
         if (c < 0 || c >= V) { bad = 1; c = blank; }
         lab[s] = (int)c;
     }
@@ -84,7 +102,7 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
         for (int i = 0; i < n; ++i) {
             const int ts = t0 + i;
             const int t = mirror ? Tb - 1 - ts : ts;
-            float* orow = out ? out + ((long long)b * T + t) * S_max : nullptr;
+            float* orow = out ? out + ((long long)item * T + t) * S_max : nullptr;
             for (int s = tid; s < S; s += nt) {
                 float v;
                 if (ts == 0) {
@@ -112,8 +130,9 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
             if (m == -INFINITY) m = 0.f;
             r = -(logf(expf(l1 - m) + expf(l2 - m)) + m);
         }
+        if (NBEST && dead) r = INFINITY;                  // an out item with T_b = 0 too
         if (zero_infinity && r == INFINITY) r = 0.f;
-        nll[b] = r;
+        nll[item] = r;
     }
 }
 
@@ -231,6 +250,145 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void ctc_nbest_grad_kernel(const float* __restrict__ lp, long long stride_b, long long stride_t,
+                                                             const int* __restrict__ hyp_ids, long long ld_b, long long ld_n,
+                                                             const long long* __restrict__ hyp_lens,
+                                                             const long long* __restrict__ input_lengths, int N, int T, int V, int S_max,
+                                                             int blank, const float* __restrict__ nll, const float* __restrict__ log_alpha,
+                                                             const float* __restrict__ log_beta, const float* __restrict__ grad_nll,
+                                                             float* __restrict__ grad, int vec) {
+    extern __shared__ float smem[];
+    const int W = blockDim.x >> 6;
+    const int Lmax = (S_max - 1) / 2;
+    float* occ_all = smem;                                // [W][V]     sum over the hypotheses of g_n occ_n of the wavefront's row
+    float* ab_all = smem + (long long)W * V;              // [W][S_max] alpha + beta + nll of the row and the current hypothesis
+    int* lab = (int*)(ab_all + W * S_max);                // [N][Lmax] labels; nxt, own as in ctc_grad_kernel, per hypothesis
+    int* nxt = lab + N * Lmax;
+    int* own = nxt + N * Lmax;
+    int* hl = own + N * Lmax;                             // [N] length of the hypothesis, -1 = out
+    float* hg = (float*)(hl + N);                         // [N] its grad_nll (0 when out: the value is never read then)
+    float* hn = hg + N;                                   // [N] its nll
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.y;
+    const int Tb = ctc_clamp_len(input_lengths[b], T);
+    for (int n = tid; n < N; n += nt) {
+        const long long item = (long long)b * N + n;
+        const long long Lraw = hyp_lens[item];
+        // not out <=> the length is in [0, Lmax] and the forward reached one of the two final states (a bad id leaves the lattice all -inf)
+        bool ok = Lraw >= 0 && Lraw <= Lmax && Tb > 0;
+        if (ok) {
+            const int S = 2 * (int)Lraw + 1;
+            const float* last = log_alpha + (item * T + (Tb - 1)) * S_max;
+            const float l1 = last[S - 1], l2 = S > 1 ? last[S - 2] : -INFINITY;
+            ok = l1 > -INFINITY || l2 > -INFINITY;
+        }
+        hl[n] = ok ? (int)Lraw : -1;
+        hg[n] = ok ? grad_nll[item] : 0.f;
+        hn[n] = ok ? nll[item] : 0.f;
+    }
+    for (int i = tid; i < W * V; i += nt) occ_all[i] = 0.f;
+    __syncthreads();
+    float G = 0.f;                                        // sum of g_n over the items that are not out, ascending n
+    bool any = false;
+    for (int n = 0; n < N; ++n)
+        if (hl[n] >= 0) { G += hg[n]; any = true; }
+    for (int i = tid; i < N * Lmax; i += nt) {
+        const int n = i / Lmax, k = i - n * Lmax;
+        if (k < hl[n]) {
+            const int c = hyp_ids[(long long)b * ld_b + (long long)n * ld_n + k];
+            lab[i] = (c < 0 || c >= V) ? blank : c;       // (a bad id makes the item out: never reached with the forward's own lattice)
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < N * Lmax; i += nt) {
+        const int n = i / Lmax, k = i - n * Lmax, Ln = hl[n];
+        if (k < Ln) {
+            const int* ln = lab + n * Lmax;
+            const int mine = ln[k];
+            int nx = -1, first = mine != blank;           // a label equal to the blank class is summed with the blank states
+            for (int kp = Ln - 1; kp >= 0; --kp) {
+                const int l = ln[kp];
+                if (l == mine && kp > k) nx = kp;
+                if (l == mine && kp < k) first = 0;
+            }
+            nxt[i] = nx;
+            own[i] = first;
+        }
+    }
+    float* occ = occ_all + (long long)w * V;
+    float* ab = ab_all + w * S_max;
+    const float* base = lp + (long long)b * stride_b;
+    for (int it = 0; it < CTC_BWD_ROWS; ++it) {
+        const int t = (blockIdx.x * CTC_BWD_ROWS + it) * W + w;
+        const bool act = any && t < Tb;
+        const float* row = base + (long long)t * stride_t;
+        for (int n = 0; n < N; ++n) {                     // hl[] is the same for every wavefront: the barriers below are uniform
+            const int Ln = hl[n];
+            if (Ln < 0) continue;
+            const int S = 2 * Ln + 1;
+            __syncthreads();                              // ab (previous hypothesis) is no longer read; first pass: chains are visible
+            if (act) {
+                const long long r = (((long long)b * N + n) * T + t) * S_max;
+                const float nl = hn[n];
+                for (int s = lane; s < S; s += 64) ab[s] = (log_alpha[r + s] + log_beta[r + s]) + nl;
+            }
+            __syncthreads();
+            if (act) {
+                const int* ln = lab + n * Lmax;
+                const int* nn = nxt + n * Lmax;
+                const int* on = own + n * Lmax;
+                const float g = hg[n];
+                const float lpb = row[blank];
+                float acc = 0.f;
+                for (int s = lane; s < S; s += 64) {
+                    const int c = (s & 1) ? ln[s >> 1] : blank;
+                    if (c == blank) acc += expf(ab[s] - lpb);
+                }
+                acc = wave_sum(acc);
+                if (lane == 0) occ[blank] += g * acc;
+                for (int k = lane; k < Ln; k += 64) {
+                    if (on[k]) {
+                        const int c = ln[k];
+                        const float l = row[c];
+                        float sum = 0.f;
+                        int j = k;
+                        do {
+                            sum += expf(ab[2 * j + 1] - l);
+                            j = nn[j];
+                        } while (j >= 0);
+                        occ[c] += g * sum;                // one owner lane per class and hypothesis; hypotheses in ascending n
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (t < T) {                                      // every row is written; the occupancy row is left zero for the next frame
+            float* orow = grad + ((long long)b * T + t) * V;
+            if (vec) {
+                const f32x4* r4 = (const f32x4*)row;
+                f32x4* o4 = (f32x4*)occ;
+                f32x4* d4 = (f32x4*)orow;
+                for (int i = lane; i < (V >> 2); i += 64) {
+                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+                    if (act) {
+                        const f32x4 x = r4[i], o = o4[i];
+                        d.x = G * expf(x.x) - o.x; d.y = G * expf(x.y) - o.y;
+                        d.z = G * expf(x.z) - o.z; d.w = G * expf(x.w) - o.w;
+                        o4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+                    d4[i] = d;
+                }
+            } else {
+                for (int i = lane; i < V; i += 64) {
+                    float d = 0.f;
+                    if (act) { d = G * expf(row[i]) - occ[i]; occ[i] = 0.f; }
+                    orow[i] = d;
+                }
+            }
+        }
+    }
+}
+
 constexpr long long CTC_LDS_LIMIT = 64 * 1024;
 
 }  // namespace
@@ -251,8 +409,9 @@ extern "C" int av_ctc_loss_fwd(const float* log_probs, long long stride_b, long 
     AV_CHECK(lds <= CTC_LDS_LIMIT, "av_ctc_loss_fwd: S_max %d needs %lld bytes of LDS (limit %lld)", S_max, lds, CTC_LDS_LIMIT);
     const int threads = S_max >= 256 ? 256 : (S_max + 63) / 64 * 64;
     const int grid = log_beta ? 2 * B : B;
-    hipLaunchKernelGGL(ctc_lattice_kernel, dim3(grid), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs, stride_b, stride_t, targets,
-                       target_ld, input_lengths, target_lengths, B, T, V, S_max, blank, zero_infinity, nll, log_alpha, log_beta);
+    hipLaunchKernelGGL(ctc_lattice_kernel<false>, dim3(grid), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs, stride_b, stride_t,
+                       (const void*)targets, target_ld, 0LL, input_lengths, target_lengths, B, 1, T, V, S_max, blank, zero_infinity, nll,
+                       log_alpha, log_beta);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -284,6 +443,66 @@ extern "C" int av_ctc_loss_bwd(const float* log_probs, long long stride_b, long 
     hipLaunchKernelGGL(ctc_grad_kernel, dim3((T + rows - 1) / rows, B), dim3(64 * W), (size_t)lds, (hipStream_t)stream, log_probs, stride_b,
                        stride_t, targets, target_ld, input_lengths, target_lengths, T, V, S_max, blank, nll, log_alpha, log_beta, grad_nll,
                        grad, vec);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// the argument law both n-best entry points share; grid limits: the lattice launches 2 B N workgroups in x (B N <= 2^30), the gradient
+// kernel puts B in grid y (B <= 65535)
+static int ctc_nbest_check(const char* fn, long long stride_b, long long stride_t, long long hyp_ld_b, long long hyp_ld_n, int B, int N, int T,
+                           int V, int S_max, int blank) {
+    AV_CHECK(N >= 1 && N <= 64, "%s: N = %d hypotheses per utterance outside [1, 64]", fn, N);
+    AV_CHECK(B >= 1 && B <= 65535 && T >= 1 && V >= 1, "%s: bad shape B=%d T=%d V=%d (1 <= B <= 65535: the grid limit)", fn, B, T, V);
+    AV_CHECK(blank >= 0 && blank < V, "%s: blank %d outside [0, %d)", fn, blank, V);
+    AV_CHECK(S_max >= 1 && (S_max & 1), "%s: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", fn, S_max);
+    const int Lmax = (S_max - 1) / 2;
+    AV_CHECK(hyp_ld_n >= Lmax, "%s: hyp_ld_n %lld < Lmax %d", fn, hyp_ld_n, Lmax);
+    AV_CHECK(hyp_ld_b >= (long long)(N - 1) * hyp_ld_n + Lmax, "%s: hyp_ld_b %lld does not cover N = %d rows of hyp_ld_n %lld", fn, hyp_ld_b, N,
+             hyp_ld_n);
+    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b >= (long long)T * stride_t) ||
+                                                 (stride_b >= V && stride_t >= (long long)B * stride_b)),
+             "%s: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", fn, stride_b, stride_t, B, T, V);
+    return AV_OK;
+}
+
+extern "C" int av_ctc_nbest_fwd(const float* log_probs, long long stride_b, long long stride_t, const int* hyp_ids, long long hyp_ld_b,
+                                long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V,
+                                int S_max, int blank, float* nll, float* log_alpha, float* log_beta, void* stream) {
+    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll, "av_ctc_nbest_fwd: null pointer");
+    AV_CHECK(log_alpha || !log_beta, "av_ctc_nbest_fwd: log_beta without log_alpha (null pointer)");
+    if (int st = ctc_nbest_check("av_ctc_nbest_fwd", stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return st;
+    const long long lds = ((long long)(2 + CTC_TCHUNK) * S_max) * sizeof(float) + 2LL * S_max * sizeof(int);
+    AV_CHECK(lds <= CTC_LDS_LIMIT, "av_ctc_nbest_fwd: S_max %d needs %lld bytes of LDS (limit %lld)", S_max, lds, CTC_LDS_LIMIT);
+    const int threads = S_max >= 256 ? 256 : (S_max + 63) / 64 * 64;
+    const int items = B * N;                              // <= 65535 * 64
+    hipLaunchKernelGGL(ctc_lattice_kernel<true>, dim3(log_beta ? 2 * items : items), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs,
+                       stride_b, stride_t, (const void*)hyp_ids, hyp_ld_b, hyp_ld_n, input_lengths, hyp_lens, items, N, T, V, S_max, blank, 0,
+                       nll, log_alpha, log_beta);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_ctc_nbest_bwd(const float* log_probs, long long stride_b, long long stride_t, const int* hyp_ids, long long hyp_ld_b,
+                                long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V,
+                                int S_max, int blank, const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll,
+                                float* grad, void* stream) {
+    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll && log_alpha && log_beta && grad_nll && grad,
+             "av_ctc_nbest_bwd: null pointer");
+    if (int st = ctc_nbest_check("av_ctc_nbest_bwd", stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return st;
+    const int Lmax = (S_max - 1) / 2;
+    int W = 4;                                            // wavefronts (= rows in flight) per workgroup: as many as the LDS rows allow
+    long long lds = 0;
+    for (; W >= 1; W >>= 1) {
+        lds = (long long)W * ((long long)V + S_max) * sizeof(float) + 3LL * N * Lmax * sizeof(int) + 3LL * N * sizeof(int);
+        if (lds <= CTC_LDS_LIMIT) break;
+    }
+    AV_CHECK(W >= 1, "av_ctc_nbest_bwd: V %d + S_max %d floats and 3 N Lmax = %lld label ints exceed the LDS (limit %lld bytes)", V, S_max,
+             3LL * N * Lmax, CTC_LDS_LIMIT);
+    const int vec = (V % 4 == 0) && (stride_b % 4 == 0) && (stride_t % 4 == 0) && ((uintptr_t)log_probs % 16 == 0) && ((uintptr_t)grad % 16 == 0);
+    const int rows = W * CTC_BWD_ROWS;
+    hipLaunchKernelGGL(ctc_nbest_grad_kernel, dim3((T + rows - 1) / rows, B), dim3(64 * W), (size_t)lds, (hipStream_t)stream, log_probs,
+                       stride_b, stride_t, hyp_ids, hyp_ld_b, hyp_ld_n, hyp_lens, input_lengths, N, T, V, S_max, blank, nll, log_alpha, log_beta,
+                       grad_nll, grad, vec);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -79,7 +79,8 @@ class MultimodalTrainer:
                  visual_side_stream: bool = True, loss_scaling: bool = False, native_ctc: Optional[bool] = None,
                  eval_beam_width: Optional[int] = None, eval_lm=None, eval_lm_weight: Optional[float] = None,
                  eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None, eval_bias=None,
-                 eval_bias_weight: Optional[float] = None):
+                 eval_bias_weight: Optional[float] = None, mwer_weight: Optional[float] = None, mwer_nbest: Optional[int] = None,
+                 mwer_beam: Optional[int] = None, mwer_level: str = "word"):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -130,6 +131,21 @@ class MultimodalTrainer:
         # (default "0"); off: none of that code runs
         self.eval_report = os.environ.get("AVAMD_EVAL_REPORT", "0") == "1" if eval_report is None else bool(eval_report)
         self.last_report = None
+        # opt-in: minimum word error rate training (mwer.mwer_loss: n-best beam search, error counts and the n-best CTC loss of
+        # csrc/ctc_loss.hip, all on the device).  With mwer_weight > 0 and gradients enabled forward_losses adds
+        # mwer_weight * (mwer1 + mwer2) / 2 to ``total``; evaluate()'s loss stays the CTC loss.  None reads AVAMD_MWER_WEIGHT (default "0"),
+        # AVAMD_MWER_NBEST (4) and AVAMD_MWER_BEAM (8); weight 0: none of that code runs
+        self.mwer_weight = float(os.environ.get("AVAMD_MWER_WEIGHT", "0")) if mwer_weight is None else float(mwer_weight)
+        self.mwer_nbest = int(os.environ.get("AVAMD_MWER_NBEST", "4")) if mwer_nbest is None else int(mwer_nbest)
+        self.mwer_beam = int(os.environ.get("AVAMD_MWER_BEAM", "8")) if mwer_beam is None else int(mwer_beam)
+        self.mwer_level = mwer_level
+        if not 0.0 <= self.mwer_weight < float("inf"):         # NaN fails both comparisons
+            raise ValueError(f"mwer_weight must be finite and >= 0, got {self.mwer_weight}")
+        if not 1 <= self.mwer_nbest <= self.mwer_beam <= 64:
+            raise ValueError(f"need 1 <= mwer_nbest <= mwer_beam <= 64, got mwer_nbest={self.mwer_nbest} mwer_beam={self.mwer_beam}")
+        if mwer_level not in ("word", "char", "token"):
+            raise ValueError(f"mwer_level must be 'word', 'char' or 'token', got {mwer_level!r}")
+        self._mwer_table = None                                # the tokenizer's PieceTable, built once when the term first runs
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.optimizer = AvAdam([
@@ -368,9 +384,28 @@ class MultimodalTrainer:
                 l2 = self.ctc_loss(lp2.transpose(0, 1), d["text2"], il2, d["text2_lengths"])
         if total is None:
             total = (l1 + l2) / 2 + self.lambda_ * (c1 + c2) / 2
+        if self.mwer_weight > 0 and torch.is_grad_enabled():
+            # the MWER term meets the CTC term at the log-probs through autograd, as the contrastive and CTC terms meet further down
+            if pair:
+                per = self._mwer(lp12, tg, tl, il12)
+                mw1, mw2 = per[:B].mean(), per[B:].mean()
+            else:
+                mw1 = self._mwer(lp1, d["text1"], d["text1_lengths"], il1).mean()
+                mw2 = self._mwer(lp2, d["text2"], d["text2_lengths"], il2).mean()
+            total = total + self.mwer_weight * (mw1 + mw2) / 2
+            out.update(mwer1=mw1, mwer2=mw2)
         out.update(visual_feat1=vf1, visual_feat2=vf2, audio_last=a1, audio_mid=mid1, fused1=f1, fused2=f2, input_lengths1=il1,
                    input_lengths2=il2, log_probs1=lp1, log_probs2=lp2, loss1=l1, loss2=l2, contrast1=c1, contrast2=c2, total=total)
         return out
+
+    def _mwer(self, lp, refs, ref_lengths, input_lengths):
+        """Per-utterance MWER risk [B] of one decoder call (mwer.mwer_loss, reduction "none"); float32 log-probs as the CTC loss reads them."""
+        from ..mwer import mwer_loss
+        if self.mwer_level != "token" and self._mwer_table is None:
+            from ..error_rate import PieceTable
+            self._mwer_table = PieceTable.from_tokenizer(self.tokenizer)
+        return mwer_loss(lp.float(), refs, ref_lengths, input_lengths, self.tokenizer.blank_id, nbest=self.mwer_nbest,
+                         beam_width=self.mwer_beam, table=self._mwer_table, level=self.mwer_level, reduction="none")
 
     def train_step(self, batch) -> Dict[str, torch.Tensor]:
         """zero_grad -> forward -> backward (-> bucketed all-reduce) -> Adam; no host sync."""

@@ -639,6 +639,88 @@ def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, 
     return (nll / tl.clamp_min(1).to(torch.float32)).mean()
 
 
+class _CtcNbestFn(torch.autograd.Function):
+    """nll [B, N] = av_ctc_nbest_fwd; d (sum g nll) / d log_probs = av_ctc_nbest_bwd: one [B, T, V] gradient for the N hypotheses."""
+
+    @staticmethod
+    def forward(fctx, log_probs, hyp_ids, hyp_lengths, input_lengths, blank, batch_first, S_max):
+        lp = log_probs.detach()
+        if lp.stride(2) != 1:
+            lp = lp.contiguous()
+        if batch_first:
+            (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
+        else:
+            (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+        N, Lh = hyp_ids.shape[1], hyp_ids.shape[2]
+        Lmax = (S_max - 1) // 2
+        ld_n = hyp_ids.stride(1) if N > 1 else max(Lh, 1)
+        ld_b = hyp_ids.stride(0) if B > 1 else (N - 1) * ld_n + max(Lh, 1)
+        need = fctx.needs_input_grad[0]
+        nll = torch.empty((B, N), dtype=torch.float32, device=lp.device)
+        la = torch.empty((B, N, T, S_max), dtype=torch.float32, device=lp.device) if need else None
+        lb = torch.empty((B, N, T, S_max), dtype=torch.float32, device=lp.device) if need else None
+        L.check(L.lib().av_ctc_nbest_fwd(ptr(lp), sb, st, ptr(hyp_ids), ld_b, ld_n, ptr(hyp_lengths), ptr(input_lengths), B, N, T, V, S_max,
+                                         int(blank), ptr(nll), ptr(la), ptr(lb), stream()), "av_ctc_nbest_fwd")
+        if need:
+            fctx.save_for_backward(lp, hyp_ids, hyp_lengths, input_lengths, nll, la, lb)
+            fctx.cfg = (B, N, T, V, S_max, sb, st, ld_b, ld_n, int(blank), bool(batch_first))
+        return nll
+
+    @staticmethod
+    def backward(fctx, g):
+        lp, hi, hl, il, nll, la, lb = fctx.saved_tensors
+        B, N, T, V, S_max, sb, st, ld_b, ld_n, blank, batch_first = fctx.cfg
+        g = g.contiguous().float()
+        grad = torch.empty((B, T, V), dtype=torch.float32, device=lp.device)
+        L.check(L.lib().av_ctc_nbest_bwd(ptr(lp), sb, st, ptr(hi), ld_b, ld_n, ptr(hl), ptr(il), B, N, T, V, S_max, blank, ptr(nll), ptr(la),
+                                         ptr(lb), ptr(g), ptr(grad), stream()), "av_ctc_nbest_bwd")
+        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None
+
+
+def ctc_nbest_nll(log_probs: Tensor, hyp_ids: Tensor, hyp_lengths, input_lengths, blank: int = 0, batch_first: bool = True,
+                  max_len: Optional[int] = None) -> Tensor:
+    """CTC negative log-likelihood of N label sequences per utterance against one shared block of log-probs (csrc/ctc_loss.hip, the n-best
+    form): fp32 [B, N], differentiable with respect to ``log_probs`` - the N hypotheses' gradients arrive as ONE [B, T, V] tensor, the
+    log-probs are never expanded.  ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]); any view with a contiguous last
+    dimension is taken without a copy.  ``hyp_ids`` integer [B, N, Lh] (an int32 view with unit inner stride is taken without a copy: the
+    beam kernel's id block as it is), ``hyp_lengths`` [B, N], ``input_lengths`` [B] (one per utterance, shared by its hypotheses); lengths
+    on the host are copied without blocking, nothing synchronises.  A hypothesis is OUT - nll = +inf, no gradient, the incoming gradient at
+    that position never read - when its length is < 0 (absent) or > ``max_len`` (not clamped), when an id is outside [0, V) or when no path
+    exists.  ``max_len`` (default Lh) sets the lattice width S_max = 2 max_len + 1 for callers who want smaller workspaces; every other
+    hypothesis' nll is bit for bit ``ctc_loss(..., reduction="none", zero_infinity=False)`` of that item."""
+    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
+        raise RuntimeError("ctc_nbest_nll (HIP): log_probs must be on the GPU; there is no CPU fallback")
+    if log_probs.dim() != 3:
+        raise ValueError(f"ctc_nbest_nll: log_probs must be [B, T, V] (or [T, B, V] with batch_first=False), got shape {tuple(log_probs.shape)}")
+    if log_probs.dtype != torch.float32:
+        raise TypeError(f"ctc_nbest_nll: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
+    B = log_probs.shape[0 if batch_first else 1]
+    if not isinstance(hyp_ids, Tensor) or hyp_ids.dim() != 3 or hyp_ids.shape[0] != B:
+        raise ValueError(f"ctc_nbest_nll: hyp_ids must be an integer tensor [B={B}, N, Lh], got "
+                         f"{tuple(hyp_ids.shape) if isinstance(hyp_ids, Tensor) else type(hyp_ids).__name__}")
+    if hyp_ids.dtype.is_floating_point or hyp_ids.dtype.is_complex or hyp_ids.dtype == torch.bool:
+        raise TypeError(f"ctc_nbest_nll: hyp_ids must be an integer tensor, got {hyp_ids.dtype}")
+    N, Lh = hyp_ids.shape[1], hyp_ids.shape[2]
+    if not 1 <= N <= 64:
+        raise ValueError(f"ctc_nbest_nll: N = {N} hypotheses per utterance outside [1, 64]")
+    max_len = Lh if max_len is None else int(max_len)
+    if not 0 <= max_len <= Lh:
+        raise ValueError(f"ctc_nbest_nll: max_len {max_len} outside [0, Lh = {Lh}]")
+    dev = log_probs.device
+    hi = hyp_ids.to(device=dev, dtype=torch.int32, non_blocking=True)
+    if Lh == 0:
+        hi = torch.zeros((B, N, 1), dtype=torch.int32, device=dev)
+    elif hi.stride(2) != 1 or (N > 1 and hi.stride(1) < Lh) or (B > 1 and hi.stride(0) < (N - 1) * (hi.stride(1) if N > 1 else Lh) + Lh):
+        hi = hi.contiguous()
+    if not isinstance(hyp_lengths, Tensor):
+        hyp_lengths = torch.as_tensor(hyp_lengths, dtype=torch.long)
+    if hyp_lengths.dtype.is_floating_point or hyp_lengths.dtype == torch.bool or hyp_lengths.numel() != B * N:
+        raise ValueError(f"ctc_nbest_nll: hyp_lengths must hold [B={B}, N={N}] integer lengths, got {hyp_lengths.dtype} {tuple(hyp_lengths.shape)}")
+    hl = hyp_lengths.reshape(B, N).to(device=dev, dtype=torch.long, non_blocking=True).contiguous()
+    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
+    return _CtcNbestFn.apply(log_probs, hi, hl, il, int(blank), bool(batch_first), 2 * max_len + 1)
+
+
 def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, batch_first: bool = False):
     """CTC forced alignment on the kernel of csrc/ctc_align.hip, arguments as for ``ctc_loss``: ``log_probs`` fp32 [T, B, V]
     (``batch_first``: [B, T, V]), any view with a contiguous last dimension is taken without a copy; ``targets`` integer [B, Lmax], padded;
