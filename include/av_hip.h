@@ -460,6 +460,25 @@ int av_adam_step(float* p, const float* g, float* m, float* v, long long n, floa
 int av_adam_multi(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
                   int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
                   float* scaler_state, float growth, float backoff, int growth_interval, void* stream);
+/* av_adam_multi with global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, both decided on the device
+ * (csrc/loss_misc.hip; optim.AvAdam).  The arguments of av_adam_multi, and:
+ * max_norm > 0: clip.  One more pass reads the gradients (sum of squares per chunk in double, no atomics: the same bits on every run),
+ *   one workgroup adds the chunk sums in a fixed order, and the Adam kernel multiplies grad * grad_scale (/ scale) by
+ *   min(1, max_norm / (norm + 1e-6)), the law of torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False (a NaN norm gives a NaN
+ *   coefficient, an infinite one 0).  Under loss scaling that pass also is the non-finite check.  0: no clipping, no such pass.
+ * warmup_steps, total_steps: optimizer step k (0-based, skipped steps not counted) runs at lr * k / warmup_steps while k < warmup_steps,
+ *   then at lr * max(0, (total_steps - k) / (total_steps - warmup_steps)); total_steps == 0: lr after the warmup; both 0: no schedule.
+ *   total_steps must be 0 or above warmup_steps.  One multiplier for all tensors; hyper keeps the per-tensor lr.
+ * clip_state: 4 device words, 4-byte aligned, needed when either is on: float norm of the gradients as Adam sees them, float clip
+ *   coefficient (1 without clipping), float learning-rate multiplier of this step, int32 k (the caller zeroes or restores it; the launch
+ *   advances it when a schedule is on and the step was not skipped).
+ * workspace: av_grad_norm_workspace_bytes(n_chunks) bytes, 8-byte aligned, needed when clipping; a smaller one is an error status.
+ * With max_norm, warmup_steps and total_steps all 0 this is av_adam_multi.  No host synchronisation. */
+int av_grad_norm_workspace_bytes(int n_chunks, long long* bytes);
+int av_adam_multi_ex(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
+                     int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
+                     float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
+                     int total_steps, void* workspace, long long workspace_bytes, float* clip_state, void* stream);
 
 /* ---- legacy mel + GRU model (reference: "이전 버전/multimodal_ctc_korean.py":8-55, train loop
  * "이전 버전/train_ctc_korea.py":82-109).  Its convolutions (nn.Conv2d 3x3, :12,15) and all input / weight-gradient products run on

@@ -3,7 +3,8 @@
 //   * row log-sum-exp + row sum of the similarity matrix and the softmax-minus-uniform gradient of
 //     -log_softmax(sim).mean() (contrastive.py:33-34,41-42),
 //   * scalar reductions,
-//   * fused Adam step (torch.optim.Adam defaults, model/trainer.py:34-39) with optional gradient scaling.
+//   * fused Adam step (torch.optim.Adam defaults, model/trainer.py:34-39) with optional gradient scaling, and opt-in global-norm
+//     gradient clipping and learning-rate schedule decided on the device (av_adam_multi_ex).
 #include "av_common.h"
 
 namespace {
@@ -162,6 +163,93 @@ __global__ __launch_bounds__(256) void grad_check_multi_kernel(const unsigned lo
     if (__any(bad) && (threadIdx.x & 63) == 0) gs[GS_INF] = 1.0f;          // every writer stores the same value
 }
 
+// Global-norm gradient clipping and the learning-rate schedule of av_adam_multi_ex.  Clip / schedule state on the device, four 32-bit
+// words:
+//   cs[CS_NORM]  float  L2 norm of the gradients as the Adam kernel sees them (grad * grad_scale, / scale under loss scaling),
+//   cs[CS_COEF]  float  min(1, max_norm / (norm + 1e-6)) in fp32 - torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False; nothing
+//                       is special-cased: a NaN norm gives NaN, an infinite one 0; 1 when clipping is off,
+//   cs[CS_LRM]   float  learning-rate multiplier of this step (lr_multiplier below),
+//   cs[CS_K]     int32  optimizer steps taken so far on the schedule (advanced by adam_finish_kernel, not by a skipped step).
+enum { CS_NORM = 0, CS_COEF = 1, CS_LRM = 2, CS_K = 3 };
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// sum over the workgroup in a fixed order (valid in thread 0)
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// partial[c] = sum of g^2 over chunk c of the Adam launch's tables, accumulated in double: the square of an fp32 value is exact in fp64
+// and cannot overflow it, so the sum is non-finite if and only if an element is, and the norm is good to an fp32 ulp.  The kernel is
+// bound by reading the gradients; no atomics, a fixed order of additions: the same bits on every run.
+__global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const unsigned long long* __restrict__ ptrs, const long long* __restrict__ sizes,
+                                                               const int* __restrict__ chunk_tensor, const long long* __restrict__ chunk_start,
+                                                               int chunk_elems, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    const int t = chunk_tensor[c];
+    const float* g = (const float*)ptrs[5 * t + 1];
+    const long long n = sizes[t];
+    const long long s0 = chunk_start[c];
+    long long s1 = s0 + chunk_elems;
+    if (s1 > n) s1 = n;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    long long i = s0;
+    if (((uintptr_t)g % 16 == 0) && (s0 % 4 == 0)) {
+        const long long nv = (s1 - s0) / 4;
+#pragma unroll 4
+        for (long long q = threadIdx.x; q < nv; q += 256) {
+            const f32x4 gg = *(const f32x4*)(g + s0 + 4 * q);
+            const double x0 = gg[0], x1 = gg[1], x2 = gg[2], x3 = gg[3];
+            a0 = fma(x0, x0, a0); a1 = fma(x1, x1, a1); a2 = fma(x2, x2, a2); a3 = fma(x3, x3, a3);
+        }
+        i = s0 + 4 * nv;
+    }
+    for (i += threadIdx.x; i < s1; i += 256) { const double x = g[i]; a0 = fma(x, x, a0); }
+    const double s = block_sum_f64((a0 + a1) + (a2 + a3), red);
+    if (threadIdx.x == 0) partial[c] = s;
+}
+
+// HF get_linear_schedule_with_warmup under LambdaLR: step k (0-based, steps actually taken) runs at k / warmup below warmup, then at
+// max(0, (total - k) / (total - warmup)); total == 0: constant 1 after the warmup.  optim.lr_multiplier is the same law on the host.
+__device__ __forceinline__ float lr_multiplier(int k, int warmup, int total) {
+    if (k < warmup) return (float)((double)k / (double)warmup);
+    if (total == 0) return 1.f;
+    const double m = (double)(total - k) / (double)(total - warmup);
+    return (float)(m > 0.0 ? m : 0.0);
+}
+
+// one workgroup: the chunk partials summed in a fixed order -> norm, clip coefficient, found_inf (with clipping this pass replaces
+// grad_check_multi_kernel), and this step's learning-rate multiplier.  partial == NULL: clipping is off (schedule only).
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ partial, int n_chunks, float gscale, float max_norm,
+                                                            int warmup, int total, float* __restrict__ gs, float* __restrict__ cs) {
+    __shared__ double red[4];
+    double a = 0.0;
+    if (partial)
+        for (int i = threadIdx.x; i < n_chunks; i += 256) a += partial[i];
+    const double ss = block_sum_f64(a, red);
+    if (threadIdx.x != 0) return;
+    float norm = 0.f, coef = 1.f;
+    if (partial) {
+        if (gs) {
+            if (!(ss - ss == 0.0)) gs[GS_INF] = 1.0f;
+            gscale *= gs[GS_INV];
+        }
+        norm = (float)(sqrt(ss) * (double)fabsf(gscale));
+        coef = max_norm / (norm + 1e-6f);
+        coef = coef > 1.f ? 1.f : coef;                           // a NaN stays (torch.clamp(max=1.0))
+    }
+    cs[CS_NORM] = norm;
+    cs[CS_COEF] = coef;
+    cs[CS_LRM] = lr_multiplier(((const int*)cs)[CS_K], warmup, total);
+}
+
 // torch/amp/grad_scaler.py:update (_amp_update_scale_) is applied by adam_finish_kernel below: found_inf -> scale *= backoff, tracker = 0;
 // otherwise tracker += 1 and scale *= growth when it reaches the interval; it also counts the optimizer steps that were not skipped.
 
@@ -173,10 +261,15 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
                                                          const f32x4* __restrict__ hyper, const int* __restrict__ chunk_tensor,
                                                          const long long* __restrict__ chunk_start, int chunk_elems,
                                                          const int* __restrict__ steps, const int* __restrict__ step_slot, float gscale,
-                                                         const float* __restrict__ gs) {
+                                                         const float* __restrict__ gs, const float* __restrict__ cs) {
     if (gs) {                                                    // loss scaling: skip on overflow, unscale
         if (gs[GS_INF] != 0.f) return;
         gscale *= gs[GS_INV];
+    }
+    float lr_mult = 1.f;
+    if (cs) {                                                    // av_adam_multi_ex: clip by the global norm, follow the schedule
+        gscale *= cs[CS_COEF];
+        lr_mult = cs[CS_LRM];
     }
     const int c = blockIdx.x;
     const int t = chunk_tensor[c];
@@ -194,7 +287,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
     const long long s0 = chunk_start[c];
     long long s1 = s0 + chunk_elems;
     if (s1 > n) s1 = n;
-    const float step_size = hp[0] / bc1;
+    const float step_size = cs ? hp[0] * lr_mult / bc1 : hp[0] / bc1;
     const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0) && ((uintptr_t)sh % 8 == 0) && (s0 % 4 == 0);
     long long i = s0;
     if (vec) {
@@ -224,13 +317,15 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
 }
 
 // after the Adam launch (stream order): the tensors of that launch have taken one more step - unless the step was skipped for overflow.
-// With a scaler this launch also applies the GradScaler update law (one thread).
+// With a scaler this launch also applies the GradScaler update law (one thread); sched_k (optional) is the schedule's step counter.
 __global__ void adam_finish_kernel(int* __restrict__ steps, const int* __restrict__ step_slot, int n_tensors, float* __restrict__ gs,
-                                   float growth, float backoff, int interval) {
+                                   float growth, float backoff, int interval, int* __restrict__ sched_k) {
     const bool skipped = gs && gs[GS_INF] != 0.f;
     __syncthreads();                                              // everyone has read found_inf before thread 0 clears it
-    if (!skipped)
+    if (!skipped) {
         for (int t = threadIdx.x; t < n_tensors; t += blockDim.x) steps[step_slot[t]] += 1;
+        if (sched_k && threadIdx.x == 0) sched_k[0] += 1;
+    }
     if (gs && threadIdx.x == 0) {
         if (skipped) {
             gs[GS_SCALE] *= backoff;
@@ -322,24 +417,66 @@ extern "C" int av_adam_step(float* p, const float* g, float* m, float* v, long l
     return AV_OK;
 }
 
-extern "C" int av_adam_multi(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
-                             int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
-                             float* scaler_state, float growth, float backoff, int growth_interval, void* stream) {
+namespace {
+
+int adam_multi_impl(const char* who, const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor,
+                    const long long* chunk_start, int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors,
+                    float grad_scale, float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
+                    int total_steps, void* workspace, long long workspace_bytes, float* clip_state, void* stream) {
     AV_CHECK(ptrs && sizes && hyper && chunk_tensor && chunk_start && steps && step_slot && n_chunks >= 0 && n_tensors >= 0 && chunk_elems > 0,
-             "av_adam_multi: bad args");
-    AV_CHECK(((uintptr_t)hyper % 16) == 0, "av_adam_multi: hyper must be 16-byte aligned ([n_tensors][4] floats)");
-    AV_CHECK(!scaler_state || growth_interval >= 1, "av_adam_multi: bad growth interval");
+             "%s: bad args", who);
+    AV_CHECK(((uintptr_t)hyper % 16) == 0, "%s: hyper must be 16-byte aligned ([n_tensors][4] floats)", who);
+    AV_CHECK(!scaler_state || growth_interval >= 1, "%s: bad growth interval", who);
+    AV_CHECK(max_norm >= 0.f, "%s: max_norm must be >= 0 and not NaN (0 = no clipping)", who);
+    AV_CHECK(warmup_steps >= 0 && total_steps >= 0 && (total_steps == 0 || total_steps > warmup_steps),
+             "%s: bad schedule (warmup_steps %d, total_steps %d: total_steps must be 0 or above warmup_steps)", who, warmup_steps, total_steps);
+    const bool clip = max_norm > 0.f, sched = warmup_steps > 0 || total_steps > 0;
+    AV_CHECK(!(clip || sched) || clip_state, "%s: clipping or a schedule needs the state block", who);
+    AV_CHECK(!(clip || sched) || ((uintptr_t)clip_state % 4) == 0, "%s: the state block must be 4-byte aligned", who);
+    AV_CHECK(!clip || (workspace && ((uintptr_t)workspace % 8) == 0 && workspace_bytes >= 8LL * n_chunks),
+             "%s: clipping needs a workspace of av_grad_norm_workspace_bytes(n_chunks) bytes, 8-byte aligned", who);
+    float* cs = (clip || sched) ? clip_state : nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (n_chunks > 0) {
-        if (scaler_state)
+        if (clip)
+            hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes, chunk_tensor,
+                               chunk_start, chunk_elems, (double*)workspace);
+        else if (scaler_state)
             hipLaunchKernelGGL(grad_check_multi_kernel, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes, chunk_tensor,
                                chunk_start, chunk_elems, scaler_state);
+        if (cs)
+            hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, st, clip ? (const double*)workspace : (const double*)nullptr, n_chunks,
+                               grad_scale, max_norm, warmup_steps, total_steps, scaler_state, cs);
         hipLaunchKernelGGL(adam_multi_kernel, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes, (const f32x4*)hyper,
-                           chunk_tensor, chunk_start, chunk_elems, (const int*)steps, step_slot, grad_scale, (const float*)scaler_state);
+                           chunk_tensor, chunk_start, chunk_elems, (const int*)steps, step_slot, grad_scale, (const float*)scaler_state,
+                           (const float*)cs);
     }
     if (n_tensors > 0 || scaler_state)
         hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(256), 0, st, steps, step_slot, n_tensors, scaler_state, growth, backoff,
-                           growth_interval);
+                           growth_interval, (sched && n_chunks > 0) ? (int*)cs + CS_K : (int*)nullptr);
     AV_LAUNCH_CHECK();
     return AV_OK;
+}
+
+}  // namespace
+
+extern "C" int av_adam_multi(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
+                             int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
+                             float* scaler_state, float growth, float backoff, int growth_interval, void* stream) {
+    return adam_multi_impl("av_adam_multi", ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot, n_tensors,
+                           grad_scale, scaler_state, growth, backoff, growth_interval, 0.f, 0, 0, nullptr, 0, nullptr, stream);
+}
+extern "C" int av_grad_norm_workspace_bytes(int n_chunks, long long* bytes) {
+    AV_CHECK(bytes && n_chunks >= 0, "av_grad_norm_workspace_bytes: bad args");
+    *bytes = 8LL * (n_chunks > 0 ? n_chunks : 1);
+    return AV_OK;
+}
+extern "C" int av_adam_multi_ex(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor,
+                                const long long* chunk_start, int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors,
+                                float grad_scale, float* scaler_state, float growth, float backoff, int growth_interval, float max_norm,
+                                int warmup_steps, int total_steps, void* workspace, long long workspace_bytes, float* clip_state,
+                                void* stream) {
+    return adam_multi_impl("av_adam_multi_ex", ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot,
+                           n_tensors, grad_scale, scaler_state, growth, backoff, growth_interval, max_norm, warmup_steps, total_steps,
+                           workspace, workspace_bytes, clip_state, stream);
 }

@@ -80,7 +80,8 @@ class MultimodalTrainer:
                  eval_beam_width: Optional[int] = None, eval_lm=None, eval_lm_weight: Optional[float] = None,
                  eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None, eval_bias=None,
                  eval_bias_weight: Optional[float] = None, mwer_weight: Optional[float] = None, mwer_nbest: Optional[int] = None,
-                 mwer_beam: Optional[int] = None, mwer_level: str = "word"):
+                 mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
+                 warmup_steps: Optional[int] = None, total_steps: Optional[int] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -148,12 +149,22 @@ class MultimodalTrainer:
         self._mwer_table = None                                # the tokenizer's PieceTable, built once when the term first runs
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
+        # opt-in: global-norm gradient clipping and a linear warmup / decay of the learning rate inside the fused Adam step (optim.AvAdam,
+        # av_adam_multi_ex: norm, clip coefficient and schedule step live on the device, the step still holds no synchronising call).
+        # max_grad_norm: torch.nn.utils.clip_grad_norm_'s law; None reads AVAMD_CLIP_NORM (default "0" = off).  warmup_steps / total_steps:
+        # optim.lr_multiplier, one multiplier for all four groups (with a warmup the first step runs at multiplier 0, as torch's LambdaLR
+        # does); None reads AVAMD_WARMUP_STEPS / AVAMD_TOTAL_STEPS (default "0").  All off: none of that code runs.  Data parallel: the norm
+        # is taken after the all-reduce, over grad * grad_scale, so every rank computes the same bits from the same bytes
+        max_grad_norm = float(os.environ.get("AVAMD_CLIP_NORM", "0")) if max_grad_norm is None else float(max_grad_norm)
+        warmup_steps = int(os.environ.get("AVAMD_WARMUP_STEPS", "0")) if warmup_steps is None else int(warmup_steps)
+        total_steps = int(os.environ.get("AVAMD_TOTAL_STEPS", "0")) if total_steps is None else int(total_steps)
         self.optimizer = AvAdam([
             {"params": list(self.visual_encoder.parameters()), "lr": learning_rate},
             {"params": list(self.audio_encoder.parameters()), "lr": 2e-5},
             {"params": list(self.fusion_module.parameters()), "lr": learning_rate},
             {"params": list(self.decoder1.parameters()), "lr": learning_rate},
-        ])
+        ], max_grad_norm=max_grad_norm, warmup_steps=warmup_steps, total_steps=total_steps)     # ValueError on bad values
+        self.max_grad_norm, self.warmup_steps, self.total_steps = max_grad_norm, warmup_steps, total_steps
         # model/trainer.py:40 (GradScaler); off by default: bf16 operands need no loss scaling.  On = the reference's overflow-skip /
         # growth / backoff law, evaluated on the device
         self.scaler = AvGradScaler(device=device, enabled=loss_scaling)
@@ -408,7 +419,8 @@ class MultimodalTrainer:
                          beam_width=self.mwer_beam, table=self._mwer_table, level=self.mwer_level, reduction="none")
 
     def train_step(self, batch) -> Dict[str, torch.Tensor]:
-        """zero_grad -> forward -> backward (-> bucketed all-reduce) -> Adam; no host sync."""
+        """zero_grad -> forward -> backward (-> bucketed all-reduce) -> Adam; no host sync.  With max_grad_norm > 0 the result also has
+        ``grad_norm``: the global gradient norm before clipping, a device scalar."""
         self.optimizer.zero_grad(set_to_none=True)
         self._head_arena.begin_step()
         begin = getattr(self.audio_encoder.model, "begin_grad_step", None)
@@ -428,6 +440,8 @@ class MultimodalTrainer:
             self._head_done = False
         self.scaler.step(self.optimizer)                           # model/trainer.py:122-123 (update() is part of the device-side step)
         self.scaler.update()
+        if self.optimizer.clipping:
+            out["grad_norm"] = self.optimizer.last_grad_norm
         return out
 
     def _reduce_head_early(self):
@@ -462,6 +476,9 @@ class MultimodalTrainer:
                     print(f"[Batch {batch_idx}] CTC1: {out['loss1'].item():.4f}, CTC2: {out['loss2'].item():.4f}, "
                           f"Contrast1: {float(out['contrast1']):.4f}, Contrast2: {float(out['contrast2']):.4f}, "
                           f"Total: {out['total'].item():.4f}", flush=True)
+                    if self.optimizer.clipping or self.optimizer.scheduled:
+                        print(f"[Batch {batch_idx}] grad norm: {float(self.optimizer.last_grad_norm):.4f}, "
+                              f"LR multiplier: {float(self.optimizer.last_lr_mult):.4f}", flush=True)
             except NotImplementedError:  # a configuration this build does not cover: every later batch would fail the same way
                 raise
             except Exception as e:       # model/trainer.py:162-164: skip the batch, keep going

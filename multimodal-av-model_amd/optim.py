@@ -1,7 +1,9 @@
 """Adam with a fused HIP step kernel (torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8, no weight decay —
 model/trainer.py:34-39).  State keys (step / exp_avg / exp_avg_sq) match torch.optim.Adam, so the reference's
 checkpoint dict (main.py:47-55) stays loadable.  ``grad_scale`` folds the data-parallel 1/world_size (or a loss
-un-scale) into the step so that no extra pass over the gradients is needed."""
+un-scale) into the step so that no extra pass over the gradients is needed.  Opt-in (``max_grad_norm`` / ``warmup_steps`` /
+``total_steps``): global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, decided on the device inside
+the same fused step."""
 from __future__ import annotations
 
 import torch
@@ -53,6 +55,31 @@ class AvGradScaler:
         self.state[4] = float(sd.get("_steps_taken", 0))
 
 
+def lr_multiplier(k: int, warmup_steps: int = 0, total_steps: int = 0) -> float:
+    """Learning-rate multiplier of optimizer step ``k`` (0-based, counting steps actually taken): HF get_linear_schedule_with_warmup under
+    torch.optim.lr_scheduler.LambdaLR - k / warmup below the warmup, then max(0, (total - k) / (total - warmup)); ``total_steps == 0``:
+    constant 1 after the warmup; both 0: always 1.  The host form of the law the fused step evaluates on the device (tests, logging).
+    With a warmup step 0 runs at multiplier 0, as in torch: moments and step counts advance, the parameters do not move."""
+    k, warmup_steps, total_steps = int(k), int(warmup_steps), int(total_steps)
+    if k < warmup_steps:
+        return k / warmup_steps
+    if total_steps == 0:
+        return 1.0
+    return max(0.0, (total_steps - k) / (total_steps - warmup_steps))
+
+
+def check_clip_schedule(max_grad_norm, warmup_steps, total_steps):
+    """Validated (max_grad_norm, warmup_steps, total_steps); ValueError otherwise (the conditions of av_adam_multi_ex)."""
+    max_grad_norm, warmup_steps, total_steps = float(max_grad_norm), int(warmup_steps), int(total_steps)
+    if not max_grad_norm >= 0.0:                                # NaN fails the comparison
+        raise ValueError(f"max_grad_norm must be >= 0 (0 = no clipping), got {max_grad_norm}")
+    if warmup_steps < 0 or total_steps < 0:
+        raise ValueError(f"warmup_steps and total_steps must be >= 0, got {warmup_steps} and {total_steps}")
+    if total_steps != 0 and total_steps <= warmup_steps:
+        raise ValueError(f"total_steps must be 0 (no decay) or above warmup_steps, got total_steps={total_steps} warmup_steps={warmup_steps}")
+    return max_grad_norm, warmup_steps, total_steps
+
+
 class _Plan:
     """Static part of one multi-tensor launch (cached per set of (parameter, hyper-parameters)): sizes, {lr, beta1, beta2, eps} per tensor,
     chunk table, step-table slots - and the pointer table of its last launch (re-uploaded only when a pointer changed)."""
@@ -63,10 +90,22 @@ class AvAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics, one fused launch per step whatever the set of parameters that received a gradient: step counts are
     PER TENSOR (torch keeps ``state[p]['step']`` per parameter; LayerDrop leaves a whole layer without gradients now and then,
     hf:774-789) and live in a device table the kernel reads and a trailing one-block launch advances.  The host-side ``state[p]['step']``
-    mirrors it exactly without loss scaling; under loss scaling the device decides which steps count (``sync_steps``)."""
+    mirrors it exactly without loss scaling; under loss scaling the device decides which steps count (``sync_steps``).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    ``max_grad_norm`` > 0 clips the gradients by their global L2 norm (torch.nn.utils.clip_grad_norm_'s law, taken over the gradients as
+    the step sees them: times ``grad_scale``, un-scaled under loss scaling); ``warmup_steps`` / ``total_steps`` scale every group's ``lr``
+    by ``lr_multiplier(k)``, k = steps actually taken.  Both are evaluated on the device by ``av_adam_multi_ex`` (one more read of the
+    gradients for the norm; no host synchronisation, no new plan); ``param_groups[i]["lr"]`` stays the base rate.  All off (the default):
+    the step is ``av_adam_multi``, as before."""
+
+    SCHEDULE_KEY = "av_schedule_step"     # state_dict entry of the schedule step; torch.optim.Adam.load_state_dict ignores it
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, warmup_steps=0, total_steps=0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self.max_grad_norm, self.warmup_steps, self.total_steps = check_clip_schedule(max_grad_norm, warmup_steps, total_steps)
+        self._clip_state = None       # device block {norm, clip coefficient, lr multiplier, schedule step}, made by the first step
+        self._clip_ws = None          # one double per chunk of all parameters
+        self._sched_seed = 0          # schedule step to put into a fresh block (load_state_dict)
         self.grad_scale = 1.0
         self._plans = {}
         self._slot = None             # id(parameter) -> slot in the device step table
@@ -104,8 +143,59 @@ class AvAdam(torch.optim.Optimizer):
             self._steps_seeded = True
         return self._steps_dev
 
+    @property
+    def clipping(self) -> bool:
+        return self.max_grad_norm > 0.0
+
+    @property
+    def scheduled(self) -> bool:
+        return self.warmup_steps > 0 or self.total_steps > 0
+
+    def _clip_block(self, dev):
+        """State block and norm workspace of av_adam_multi_ex: allocated once, they live with the optimizer."""
+        if self._clip_state is None or self._clip_state.device != torch.device(dev):
+            self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
+            if self._sched_seed:
+                self._clip_state.view(torch.int32)[3:4].fill_(self._sched_seed)
+            self._clip_ws = None
+        if self._clip_ws is None:
+            nch = sum(-(-p.numel() // self.CHUNK) for group in self.param_groups for p in group["params"])
+            self._clip_ws = torch.empty(max(1, nch), dtype=torch.float64, device=dev)
+        return self._clip_state, self._clip_ws
+
+    def _clip_view(self, i):
+        return None if self._clip_state is None else self._clip_state[i]
+
+    @property
+    def last_grad_norm(self):
+        """0-dim device tensor (a view of the state block, no sync): global L2 norm of the last step's gradients as Adam saw them.  None
+        before the first step with clipping or a schedule on; 0 with clipping off."""
+        return self._clip_view(0)
+
+    @property
+    def last_clip_coef(self):
+        """0-dim device tensor: min(1, max_grad_norm / (norm + 1e-6)) of the last step."""
+        return self._clip_view(1)
+
+    @property
+    def last_lr_mult(self):
+        """0-dim device tensor: learning-rate multiplier the last step ran at."""
+        return self._clip_view(2)
+
+    def schedule_step(self) -> int:
+        """Steps taken on the schedule so far (synchronises with the device; checkpoints and diagnostics, like AvGradScaler.steps_taken)."""
+        if self._clip_state is None:
+            return self._sched_seed
+        return int(self._clip_state.view(torch.int32)[3])
+
+    def _set_schedule_step(self, k: int) -> None:
+        self._sched_seed = int(k)
+        if self._clip_state is not None:
+            self._clip_state.view(torch.int32)[3:4].fill_(self._sched_seed)
+
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        self._set_schedule_step(state_dict.get(self.SCHEDULE_KEY, 0))
         for st in self.state.values():                              # torch >= 2 stores 'step' as a tensor in its own checkpoints
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"])
@@ -116,13 +206,17 @@ class AvAdam(torch.optim.Optimizer):
         self.state.clear()
         self._steps_seeded = False
         self._keep = None
+        self._set_schedule_step(0)
 
     def state_dict(self):
         """torch.optim.Adam's format.  Under loss scaling only the device table knows the per-parameter step counts (overflowing steps are
         skipped on the device): bring the host entries up to date first, so that a checkpoint taken through this method - not only through
-        ``checkpoint_dict`` - resumes with the right bias corrections."""
+        ``checkpoint_dict`` - resumes with the right bias corrections.  With a schedule the dict also carries its step (SCHEDULE_KEY)."""
         self.sync_steps()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.scheduled:
+            sd[self.SCHEDULE_KEY] = self.schedule_step()
+        return sd
 
     def add_param_group(self, param_group):
         if getattr(self, "_steps_dev", None) is not None:
@@ -132,6 +226,7 @@ class AvAdam(torch.optim.Optimizer):
         self._steps_dev = None
         self._steps_seeded = False
         self._plans = {}
+        self._clip_ws = None                                        # sized by the chunks of all parameters
 
     def _plan(self, plist, dev) -> _Plan:
         slots = self._slots()
@@ -207,14 +302,19 @@ class AvAdam(torch.optim.Optimizer):
             pl.ptr_dev.copy_(pl.ptr_host, non_blocking=True)
             pl.ptr_evt = torch.cuda.Event(); pl.ptr_evt.record()
             pl.ptr_list = flat
+        args = [ops.ptr(pl.ptr_dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch, self.CHUNK, ops.ptr(steps),
+                ops.ptr(pl.slots), pl.n, float(self.grad_scale)]
         if scaler is not None:
-            L.check(L.lib().av_adam_multi(ops.ptr(pl.ptr_dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
-                                          self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), ops.ptr(scaler.state),
-                                          scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval, ops.stream()), "av_adam_multi")
+            args += [ops.ptr(scaler.state), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval]
         else:
-            L.check(L.lib().av_adam_multi(ops.ptr(pl.ptr_dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
-                                          self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), None, 1.0, 1.0, 1,
-                                          ops.stream()), "av_adam_multi")
+            args += [None, 1.0, 1.0, 1]
+        if self.clipping or self.scheduled:
+            cstate, ws = self._clip_block(dev)
+            L.check(L.lib().av_adam_multi_ex(*args, self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
+                                             ws.numel() * ws.element_size(), ops.ptr(cstate), ops.stream()), "av_adam_multi_ex")
+        else:
+            L.check(L.lib().av_adam_multi(*args, ops.stream()), "av_adam_multi")
+        if scaler is None:
             for _, _, st in plist:                                  # exact host mirror (with a scaler the device decides: sync_steps)
                 st["step"] = int(st["step"]) + 1
         self.fused_launches += 1
