@@ -479,6 +479,34 @@ int av_adam_multi_ex(const void* ptrs, const long long* sizes, const float* hype
                      int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
                      float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
                      int total_steps, void* workspace, long long workspace_bytes, float* clip_state, void* stream);
+/* av_adam_multi_ex that also keeps an exponential moving average (EMA) of the weights, updated inside the same Adam launch while the new
+ * parameter is still in a register (csrc/loss_misc.hip; optim.AvAdam(ema_decay=...)).  The arguments of av_adam_multi_ex, and:
+ * ema_ptrs: [n_tensors] device pointers, the fp32 average of tensor t of the launch (a table of its own: ptrs stays [n_tensors][5]).
+ * ema_only_ptrs [n_only][2] device pointers {param, ema}, ema_only_sizes [n_only], ema_only_chunk_tensor / ema_only_chunk_start
+ *   [n_ema_only_chunks] (chunks of chunk_elems, as above): tensors that have an average but no gradient in this step (LayerDrop); a light
+ *   kernel moves their average towards the unchanged parameter.  n_ema_only_chunks == 0: none, the four tables may be NULL.
+ * ema_decay in (0, 1), ema_warmup 0 / 1: update k (0-based, skipped steps not counted) runs at d_0 = 0 - the first update copies the
+ *   parameters, torch.optim.swa_utils.AveragedModel's n_averaged == 0 - then d_k = ema_decay, or min(ema_decay, (1 + k) / (10 + k)) with
+ *   ema_warmup (TensorFlow's ExponentialMovingAverage, timm's ModelEmaV2).  Per element, in fp32, after that element's Adam update:
+ *   torch.lerp(ema, p_new, w) with w = 1 - d_k, i.e. ema += w * (p_new - ema) if w < 0.5, else ema = p_new - (p_new - ema) * (1 - w).
+ * ema_state: 2 device words, 4-byte aligned: float d_k of this step (computed in double by one thread, read from here by every
+ *   workgroup), int32 k (the caller zeroes or restores it; the launch advances it unless the step was skipped).
+ * Under loss scaling a skipped step updates no average and leaves k.  No atomics: the same bits on every run.  ema_decay == 0 with no EMA
+ * tables is av_adam_multi_ex; a decay outside [0, 1) or NaN, tables without a decay, a decay without ema_ptrs or ema_state are error
+ * statuses.  No host synchronisation. */
+int av_adam_multi_ema(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
+                      int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
+                      float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
+                      int total_steps, void* workspace, long long workspace_bytes, float* clip_state, const void* ema_ptrs,
+                      const void* ema_only_ptrs, const long long* ema_only_sizes, const int* ema_only_chunk_tensor,
+                      const long long* ema_only_chunk_start, int n_ema_only_chunks, float ema_decay, int ema_warmup, float* ema_state,
+                      void* stream);
+/* one multi-tensor launch that exchanges parameters and their averages: ptrs [n_tensors][3] device pointers {param, ema, shadow}, sizes
+ * [n_tensors], chunk tables as av_adam_multi.  param and ema (fp32) change places element by element, without a temporary copy; where
+ * shadow != 0 the new parameter's 16-bit image (bf16 in libavhip.so, half in libavhip_f16.so) is written there, as the Adam kernel does.
+ * Calling it twice restores every bit. */
+int av_param_swap_multi(const void* ptrs, const long long* sizes, const int* chunk_tensor, const long long* chunk_start, int n_chunks,
+                        int chunk_elems, void* stream);
 
 /* ---- legacy mel + GRU model (reference: "이전 버전/multimodal_ctc_korean.py":8-55, train loop
  * "이전 버전/train_ctc_korea.py":82-109).  Its convolutions (nn.Conv2d 3x3, :12,15) and all input / weight-gradient products run on

@@ -8,24 +8,30 @@ import torch
 KEYS = ("epoch", "visual_encoder", "audio_encoder", "fusion", "decoder1", "optimizer")
 
 
-def checkpoint_dict(epoch: int, trainer) -> dict:
+def checkpoint_dict(epoch: int, trainer, averaged: bool = False) -> dict:
+    """``averaged``: the four module state_dicts hold the optimizer's averaged weights (AvAdam(ema_decay=...): taken under
+    ``optimizer.averaged()`` and cloned; BatchNorm buffers and parameters without an average are the trained ones); the optimizer entry is
+    the one from before the swap, so the file resumes training as an ordinary checkpoint would.  Same layout either way."""
     sc = getattr(trainer, "scaler", None)
     if sc is not None and sc.enabled:
         trainer.optimizer.sync_steps(sc)             # steps actually taken (overflowing steps are skipped on the device)
     extra = {"scaler": sc.state_dict()} if sc is not None and sc.enabled else {}
-    return {**extra,
-        "epoch": int(epoch),
-        "visual_encoder": trainer.visual_encoder.state_dict(),
-        "audio_encoder": trainer.audio_encoder.state_dict(),
-        "fusion": trainer.fusion_module.state_dict(),
-        "decoder1": trainer.decoder1.state_dict(),
-        "optimizer": trainer.optimizer.state_dict(),
-    }
+    opt = trainer.optimizer.state_dict()
+    mods = (("visual_encoder", trainer.visual_encoder), ("audio_encoder", trainer.audio_encoder), ("fusion", trainer.fusion_module),
+            ("decoder1", trainer.decoder1))
+    if averaged:
+        if not getattr(trainer.optimizer, "averaging", False):
+            raise ValueError("checkpoint_dict: averaged=True needs an optimizer that keeps an EMA (ema_decay > 0)")
+        with trainer.optimizer.averaged():
+            sds = {k: {n: v.detach().clone() for n, v in m.state_dict().items()} for k, m in mods}
+    else:
+        sds = {k: m.state_dict() for k, m in mods}
+    return {**extra, "epoch": int(epoch), **sds, "optimizer": opt}
 
 
-def save_checkpoint(epoch: int, trainer, path: str) -> None:
-    """main.py:47-55."""
-    torch.save(checkpoint_dict(epoch, trainer), path)
+def save_checkpoint(epoch: int, trainer, path: str, averaged: bool = False) -> None:
+    """main.py:47-55.  ``averaged``: save the averaged weights (checkpoint_dict)."""
+    torch.save(checkpoint_dict(epoch, trainer, averaged), path)
 
 
 def load_checkpoint(trainer, path: str, *, audio_encoder: bool = False, optimizer: bool = False) -> int:

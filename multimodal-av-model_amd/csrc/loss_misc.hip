@@ -4,7 +4,8 @@
 //     -log_softmax(sim).mean() (contrastive.py:33-34,41-42),
 //   * scalar reductions,
 //   * fused Adam step (torch.optim.Adam defaults, model/trainer.py:34-39) with optional gradient scaling, and opt-in global-norm
-//     gradient clipping and learning-rate schedule decided on the device (av_adam_multi_ex).
+//     gradient clipping and learning-rate schedule decided on the device (av_adam_multi_ex), an opt-in exponential moving average of the
+//     weights kept by the same launch (av_adam_multi_ema) and the in-place exchange of weights and averages (av_param_swap_multi).
 #include "av_common.h"
 
 namespace {
@@ -250,6 +251,34 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
     cs[CS_LRM] = lr_multiplier(((const int*)cs)[CS_K], warmup, total);
 }
 
+// Exponential moving average of the weights (av_adam_multi_ema).  EMA state on the device, two 32-bit words:
+//   es[ES_DECAY] float  decay d_k of this step's update (ema_decay_kernel below; every workgroup reads it from here),
+//   es[ES_K]     int32  EMA updates so far (advanced by adam_finish_kernel, not by a skipped step).
+enum { ES_DECAY = 0, ES_K = 1 };
+
+// one thread, the one-thread sibling of clip_finalize_kernel: d_0 = 0 (the first update copies the parameters:
+// torch.optim.swa_utils.AveragedModel's n_averaged == 0), then d_k = decay, or min(decay, (1 + k) / (10 + k)) with the warmup of
+// TensorFlow's ExponentialMovingAverage and timm's ModelEmaV2; in double, stored as a float.  optim.ema_decay is the same law on the host.
+__global__ void ema_decay_kernel(float decay, int warmup, float* __restrict__ es) {
+    const int k = ((const int*)es)[ES_K];
+    double d = 0.0;
+    if (k >= 1) {
+        d = (double)decay;
+        if (warmup) {
+            const double w = (1.0 + (double)k) / (10.0 + (double)k);
+            d = w < d ? w : d;
+        }
+    }
+    es[ES_DECAY] = (float)d;
+}
+
+// torch.lerp(ema, p, w) written out (ATen/native/Lerp.h), w = 1 - d: below 0.5 from the start point, otherwise from the end point, so
+// that w == 1 gives p exactly.  omw = 1 - w.
+__device__ __forceinline__ float ema_one(float ema, float p, float w, float omw) {
+    const float diff = p - ema;
+    return w < 0.5f ? ema + w * diff : p - diff * omw;
+}
+
 // torch/amp/grad_scaler.py:update (_amp_update_scale_) is applied by adam_finish_kernel below: found_inf -> scale *= backoff, tracker = 0;
 // otherwise tracker += 1 and scale *= growth when it reaches the interval; it also counts the optimizer steps that were not skipped.
 
@@ -257,11 +286,15 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
 // gradient in some step (LayerDrop skipped its layer in both passes: torch.optim.Adam leaves its state['step'] behind) keeps its own bias
 // corrections, every step goes through THIS kernel, and under loss scaling a skipped (overflowing) step advances no counter - all without
 // the host knowing.  hyper[t] = {lr, beta1, beta2, eps}.  Bias corrections in double (1 - beta2^step loses half its digits in fp32).
+// EMA (av_adam_multi_ema): ema_ptrs[t] is the fp32 average of tensor t, moved towards the updated parameter while that is still in a
+// register; the EMA = false instantiation is the kernel of av_adam_multi / av_adam_multi_ex, statement for statement.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long long* __restrict__ ptrs, const long long* __restrict__ sizes,
                                                          const f32x4* __restrict__ hyper, const int* __restrict__ chunk_tensor,
                                                          const long long* __restrict__ chunk_start, int chunk_elems,
                                                          const int* __restrict__ steps, const int* __restrict__ step_slot, float gscale,
-                                                         const float* __restrict__ gs, const float* __restrict__ cs) {
+                                                         const float* __restrict__ gs, const float* __restrict__ cs,
+                                                         const unsigned long long* __restrict__ ema_ptrs, const float* __restrict__ es) {
     if (gs) {                                                    // loss scaling: skip on overflow, unscale
         if (gs[GS_INF] != 0.f) return;
         gscale *= gs[GS_INV];
@@ -288,7 +321,15 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
     long long s1 = s0 + chunk_elems;
     if (s1 > n) s1 = n;
     const float step_size = cs ? hp[0] * lr_mult / bc1 : hp[0] / bc1;
-    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0) && ((uintptr_t)sh % 8 == 0) && (s0 % 4 == 0);
+    float* ema = nullptr;
+    float ew = 0.f, eomw = 0.f;                                  // lerp weight 1 - d_k and 1 - weight
+    if constexpr (EMA) {
+        ema = (float*)ema_ptrs[t];
+        ew = 1.f - es[ES_DECAY];
+        eomw = 1.f - ew;
+    }
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0) && ((uintptr_t)sh % 8 == 0) &&
+                     (s0 % 4 == 0);
     long long i = s0;
     if (vec) {
         const long long nv = (s1 - s0) / 4;
@@ -296,15 +337,19 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
             const long long e = s0 + 4 * q;
             f32x4 pp = *(const f32x4*)(p + e), mm = *(const f32x4*)(m + e), vv = *(const f32x4*)(v + e);
             const f32x4 gg = *(const f32x4*)(g + e);
+            f32x4 ee;
+            if constexpr (EMA) ee = *(const f32x4*)(ema + e);
             bf16x4 o;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float pk = pp[k], mk = mm[k], vk = vv[k];
                 o[k] = (bf16_t)adam_one(pk, gg[k], mk, vk, b1, b2, eps, step_size, bc2_sqrt, gscale);
                 pp[k] = pk; mm[k] = mk; vv[k] = vk;
+                if constexpr (EMA) ee[k] = ema_one(ee[k], pk, ew, eomw);
             }
             *(f32x4*)(p + e) = pp; *(f32x4*)(m + e) = mm; *(f32x4*)(v + e) = vv;
             if (sh) *(bf16x4*)(sh + e) = o;
+            if constexpr (EMA) *(f32x4*)(ema + e) = ee;
         }
         i = s0 + 4 * nv;
     }
@@ -313,18 +358,89 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
         const float r = adam_one(pp, g[i], mm, vv, b1, b2, eps, step_size, bc2_sqrt, gscale);
         p[i] = pp; m[i] = mm; v[i] = vv;
         if (sh) sh[i] = (bf16_t)r;
+        if constexpr (EMA) ema[i] = ema_one(ema[i], r, ew, eomw);
+    }
+}
+
+// tensors that have an EMA but received no gradient in this step (LayerDrop skipped their layer in both passes: the Adam launch does not
+// see them): ptrs[t] = {param, ema}, their own chunk tables; the average moves towards the unchanged parameter.  Skipped with the step.
+__global__ __launch_bounds__(256) void ema_only_multi_kernel(const unsigned long long* __restrict__ ptrs, const long long* __restrict__ sizes,
+                                                             const int* __restrict__ chunk_tensor, const long long* __restrict__ chunk_start,
+                                                             int chunk_elems, const float* __restrict__ gs, const float* __restrict__ es) {
+    if (gs && gs[GS_INF] != 0.f) return;
+    const float ew = 1.f - es[ES_DECAY], eomw = 1.f - ew;
+    const int c = blockIdx.x;
+    const int t = chunk_tensor[c];
+    const float* p = (const float*)ptrs[2 * t + 0];
+    float* ema = (float*)ptrs[2 * t + 1];
+    const long long n = sizes[t];
+    const long long s0 = chunk_start[c];
+    long long s1 = s0 + chunk_elems;
+    if (s1 > n) s1 = n;
+    long long i = s0;
+    if ((((uintptr_t)p | (uintptr_t)ema) % 16 == 0) && (s0 % 4 == 0)) {
+        const long long nv = (s1 - s0) / 4;
+        for (long long q = threadIdx.x; q < nv; q += 256) {
+            const long long e = s0 + 4 * q;
+            const f32x4 pp = *(const f32x4*)(p + e);
+            f32x4 ee = *(const f32x4*)(ema + e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ee[k] = ema_one(ee[k], pp[k], ew, eomw);
+            *(f32x4*)(ema + e) = ee;
+        }
+        i = s0 + 4 * nv;
+    }
+    for (i += threadIdx.x; i < s1; i += 256) ema[i] = ema_one(ema[i], p[i], ew, eomw);
+}
+
+// av_param_swap_multi: ptrs[t] = {param, ema, shadow}; param and ema change places element by element (both in registers: no temporary copy
+// of the model), and the 16-bit image of the new parameter goes to shadow (optional, 0 = none), as the Adam kernel writes it.
+__global__ __launch_bounds__(256) void param_swap_multi_kernel(const unsigned long long* __restrict__ ptrs, const long long* __restrict__ sizes,
+                                                               const int* __restrict__ chunk_tensor, const long long* __restrict__ chunk_start,
+                                                               int chunk_elems) {
+    const int c = blockIdx.x;
+    const int t = chunk_tensor[c];
+    float* p = (float*)ptrs[3 * t + 0];
+    float* ema = (float*)ptrs[3 * t + 1];
+    bf16_t* sh = (bf16_t*)ptrs[3 * t + 2];
+    const long long n = sizes[t];
+    const long long s0 = chunk_start[c];
+    long long s1 = s0 + chunk_elems;
+    if (s1 > n) s1 = n;
+    long long i = s0;
+    if ((((uintptr_t)p | (uintptr_t)ema) % 16 == 0) && ((uintptr_t)sh % 8 == 0) && (s0 % 4 == 0)) {
+        const long long nv = (s1 - s0) / 4;
+        for (long long q = threadIdx.x; q < nv; q += 256) {
+            const long long e = s0 + 4 * q;
+            const f32x4 pp = *(const f32x4*)(p + e), ee = *(const f32x4*)(ema + e);
+            *(f32x4*)(p + e) = ee; *(f32x4*)(ema + e) = pp;
+            if (sh) {
+                bf16x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = (bf16_t)ee[k];
+                *(bf16x4*)(sh + e) = o;
+            }
+        }
+        i = s0 + 4 * nv;
+    }
+    for (i += threadIdx.x; i < s1; i += 256) {
+        const float pp = p[i], ee = ema[i];
+        p[i] = ee; ema[i] = pp;
+        if (sh) sh[i] = (bf16_t)ee;
     }
 }
 
 // after the Adam launch (stream order): the tensors of that launch have taken one more step - unless the step was skipped for overflow.
-// With a scaler this launch also applies the GradScaler update law (one thread); sched_k (optional) is the schedule's step counter.
+// With a scaler this launch also applies the GradScaler update law (one thread); sched_k (optional) is the schedule's step counter, ema_k
+// (optional) the count of EMA updates.
 __global__ void adam_finish_kernel(int* __restrict__ steps, const int* __restrict__ step_slot, int n_tensors, float* __restrict__ gs,
-                                   float growth, float backoff, int interval, int* __restrict__ sched_k) {
+                                   float growth, float backoff, int interval, int* __restrict__ sched_k, int* __restrict__ ema_k) {
     const bool skipped = gs && gs[GS_INF] != 0.f;
     __syncthreads();                                              // everyone has read found_inf before thread 0 clears it
     if (!skipped) {
         for (int t = threadIdx.x; t < n_tensors; t += blockDim.x) steps[step_slot[t]] += 1;
         if (sched_k && threadIdx.x == 0) sched_k[0] += 1;
+        if (ema_k && threadIdx.x == 0) ema_k[0] += 1;
     }
     if (gs && threadIdx.x == 0) {
         if (skipped) {
@@ -419,10 +535,23 @@ extern "C" int av_adam_step(float* p, const float* g, float* m, float* v, long l
 
 namespace {
 
+// EMA arguments of av_adam_multi_ema; decay == 0 (the other entry points): off, nothing of it is read
+struct EmaArgs {
+    const void* ema_ptrs;
+    const void* only_ptrs;
+    const long long* only_sizes;
+    const int* only_chunk_tensor;
+    const long long* only_chunk_start;
+    int n_only_chunks;
+    float decay;
+    int warmup;
+    float* state;
+};
+
 int adam_multi_impl(const char* who, const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor,
                     const long long* chunk_start, int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors,
                     float grad_scale, float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
-                    int total_steps, void* workspace, long long workspace_bytes, float* clip_state, void* stream) {
+                    int total_steps, void* workspace, long long workspace_bytes, float* clip_state, const EmaArgs& ea, void* stream) {
     AV_CHECK(ptrs && sizes && hyper && chunk_tensor && chunk_start && steps && step_slot && n_chunks >= 0 && n_tensors >= 0 && chunk_elems > 0,
              "%s: bad args", who);
     AV_CHECK(((uintptr_t)hyper % 16) == 0, "%s: hyper must be 16-byte aligned ([n_tensors][4] floats)", who);
@@ -435,8 +564,18 @@ int adam_multi_impl(const char* who, const void* ptrs, const long long* sizes, c
     AV_CHECK(!(clip || sched) || ((uintptr_t)clip_state % 4) == 0, "%s: the state block must be 4-byte aligned", who);
     AV_CHECK(!clip || (workspace && ((uintptr_t)workspace % 8) == 0 && workspace_bytes >= 8LL * n_chunks),
              "%s: clipping needs a workspace of av_grad_norm_workspace_bytes(n_chunks) bytes, 8-byte aligned", who);
+    AV_CHECK(ea.decay >= 0.f && ea.decay < 1.f, "%s: ema_decay must be in [0, 1) and not NaN (0 = no EMA), got %g", who, (double)ea.decay);
+    const bool ema = ea.decay > 0.f;
+    AV_CHECK(ema || (!ea.ema_ptrs && !ea.only_ptrs && ea.n_only_chunks == 0), "%s: EMA tables without an ema_decay", who);
+    AV_CHECK(!ema || ea.ema_ptrs, "%s: ema_decay > 0 needs the EMA pointer table", who);
+    AV_CHECK(!ema || (ea.n_only_chunks >= 0 && (ea.n_only_chunks == 0 || (ea.only_ptrs && ea.only_sizes && ea.only_chunk_tensor &&
+                                                                          ea.only_chunk_start))),
+             "%s: bad EMA-only tables (%d chunks)", who, ea.n_only_chunks);
+    AV_CHECK(!ema || ea.state, "%s: ema_decay > 0 needs the EMA state block", who);
+    AV_CHECK(!ema || ((uintptr_t)ea.state % 4) == 0, "%s: the EMA state block must be 4-byte aligned", who);
     float* cs = (clip || sched) ? clip_state : nullptr;
     hipStream_t st = (hipStream_t)stream;
+    const bool ema_run = ema && (n_chunks > 0 || ea.n_only_chunks > 0);
     if (n_chunks > 0) {
         if (clip)
             hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes, chunk_tensor,
@@ -447,16 +586,31 @@ int adam_multi_impl(const char* who, const void* ptrs, const long long* sizes, c
         if (cs)
             hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, st, clip ? (const double*)workspace : (const double*)nullptr, n_chunks,
                                grad_scale, max_norm, warmup_steps, total_steps, scaler_state, cs);
-        hipLaunchKernelGGL(adam_multi_kernel, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes, (const f32x4*)hyper,
-                           chunk_tensor, chunk_start, chunk_elems, (const int*)steps, step_slot, grad_scale, (const float*)scaler_state,
-                           (const float*)cs);
     }
-    if (n_tensors > 0 || scaler_state)
+    if (ema_run) hipLaunchKernelGGL(ema_decay_kernel, dim3(1), dim3(1), 0, st, ea.decay, ea.warmup, ea.state);
+    if (n_chunks > 0) {
+        if (ema)
+            hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes,
+                               (const f32x4*)hyper, chunk_tensor, chunk_start, chunk_elems, (const int*)steps, step_slot, grad_scale,
+                               (const float*)scaler_state, (const float*)cs, (const unsigned long long*)ea.ema_ptrs, (const float*)ea.state);
+        else
+            hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(n_chunks), dim3(256), 0, st, (const unsigned long long*)ptrs, sizes,
+                               (const f32x4*)hyper, chunk_tensor, chunk_start, chunk_elems, (const int*)steps, step_slot, grad_scale,
+                               (const float*)scaler_state, (const float*)cs, (const unsigned long long*)nullptr, (const float*)nullptr);
+    }
+    if (ema && ea.n_only_chunks > 0)
+        hipLaunchKernelGGL(ema_only_multi_kernel, dim3(ea.n_only_chunks), dim3(256), 0, st, (const unsigned long long*)ea.only_ptrs,
+                           ea.only_sizes, ea.only_chunk_tensor, ea.only_chunk_start, chunk_elems, (const float*)scaler_state,
+                           (const float*)ea.state);
+    if (n_tensors > 0 || scaler_state || ema_run)
         hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(256), 0, st, steps, step_slot, n_tensors, scaler_state, growth, backoff,
-                           growth_interval, (sched && n_chunks > 0) ? (int*)cs + CS_K : (int*)nullptr);
+                           growth_interval, (sched && n_chunks > 0) ? (int*)cs + CS_K : (int*)nullptr,
+                           ema_run ? (int*)ea.state + ES_K : (int*)nullptr);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
+
+const EmaArgs kNoEma = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0, nullptr};
 
 }  // namespace
 
@@ -464,7 +618,7 @@ extern "C" int av_adam_multi(const void* ptrs, const long long* sizes, const flo
                              int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
                              float* scaler_state, float growth, float backoff, int growth_interval, void* stream) {
     return adam_multi_impl("av_adam_multi", ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot, n_tensors,
-                           grad_scale, scaler_state, growth, backoff, growth_interval, 0.f, 0, 0, nullptr, 0, nullptr, stream);
+                           grad_scale, scaler_state, growth, backoff, growth_interval, 0.f, 0, 0, nullptr, 0, nullptr, kNoEma, stream);
 }
 extern "C" int av_grad_norm_workspace_bytes(int n_chunks, long long* bytes) {
     AV_CHECK(bytes && n_chunks >= 0, "av_grad_norm_workspace_bytes: bad args");
@@ -478,5 +632,27 @@ extern "C" int av_adam_multi_ex(const void* ptrs, const long long* sizes, const 
                                 void* stream) {
     return adam_multi_impl("av_adam_multi_ex", ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot,
                            n_tensors, grad_scale, scaler_state, growth, backoff, growth_interval, max_norm, warmup_steps, total_steps,
-                           workspace, workspace_bytes, clip_state, stream);
+                           workspace, workspace_bytes, clip_state, kNoEma, stream);
+}
+extern "C" int av_adam_multi_ema(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor,
+                                 const long long* chunk_start, int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors,
+                                 float grad_scale, float* scaler_state, float growth, float backoff, int growth_interval, float max_norm,
+                                 int warmup_steps, int total_steps, void* workspace, long long workspace_bytes, float* clip_state,
+                                 const void* ema_ptrs, const void* ema_only_ptrs, const long long* ema_only_sizes,
+                                 const int* ema_only_chunk_tensor, const long long* ema_only_chunk_start, int n_ema_only_chunks,
+                                 float ema_decay, int ema_warmup, float* ema_state, void* stream) {
+    const EmaArgs ea = {ema_ptrs, ema_only_ptrs, ema_only_sizes, ema_only_chunk_tensor, ema_only_chunk_start, n_ema_only_chunks,
+                        ema_decay, ema_warmup, ema_state};
+    return adam_multi_impl("av_adam_multi_ema", ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot,
+                           n_tensors, grad_scale, scaler_state, growth, backoff, growth_interval, max_norm, warmup_steps, total_steps,
+                           workspace, workspace_bytes, clip_state, ea, stream);
+}
+extern "C" int av_param_swap_multi(const void* ptrs, const long long* sizes, const int* chunk_tensor, const long long* chunk_start,
+                                   int n_chunks, int chunk_elems, void* stream) {
+    AV_CHECK(ptrs && sizes && chunk_tensor && chunk_start && n_chunks >= 0 && chunk_elems > 0, "av_param_swap_multi: bad args");
+    if (n_chunks == 0) return AV_OK;
+    hipLaunchKernelGGL(param_swap_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)ptrs, sizes,
+                       chunk_tensor, chunk_start, chunk_elems);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
 }

@@ -81,7 +81,8 @@ class MultimodalTrainer:
                  eval_token_bonus: Optional[float] = None, eval_report: Optional[bool] = None, eval_bias=None,
                  eval_bias_weight: Optional[float] = None, mwer_weight: Optional[float] = None, mwer_nbest: Optional[int] = None,
                  mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
-                 warmup_steps: Optional[int] = None, total_steps: Optional[int] = None):
+                 warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
+                 ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -158,13 +159,26 @@ class MultimodalTrainer:
         max_grad_norm = float(os.environ.get("AVAMD_CLIP_NORM", "0")) if max_grad_norm is None else float(max_grad_norm)
         warmup_steps = int(os.environ.get("AVAMD_WARMUP_STEPS", "0")) if warmup_steps is None else int(warmup_steps)
         total_steps = int(os.environ.get("AVAMD_TOTAL_STEPS", "0")) if total_steps is None else int(total_steps)
+        # opt-in: an exponential moving average of the trainable weights kept inside the same fused step (optim.AvAdam(ema_decay=...),
+        # av_adam_multi_ema: skipped with an overflowing step on the device, moved for LayerDrop-ped layers too, no synchronising call).
+        # ema_decay: None reads AVAMD_EMA_DECAY (default "0" = off); ema_warmup: optim.ema_decay's warmup, None reads AVAMD_EMA_WARMUP
+        # ("0").  eval_ema: evaluate() and align() run with the averaged weights (optimizer.averaged(): swapped in and back in place;
+        # BatchNorm buffers are not averaged, torch.optim.swa_utils.AveragedModel's default); None reads AVAMD_EVAL_EMA ("0").  Off: none of
+        # that code runs.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated
+        ema_decay = float(os.environ.get("AVAMD_EMA_DECAY", "0")) if ema_decay is None else float(ema_decay)
+        ema_warmup = os.environ.get("AVAMD_EMA_WARMUP", "0") == "1" if ema_warmup is None else bool(ema_warmup)
+        self.eval_ema = os.environ.get("AVAMD_EVAL_EMA", "0") == "1" if eval_ema is None else bool(eval_ema)
+        if self.eval_ema and not ema_decay > 0:
+            raise ValueError("eval_ema needs ema_decay > 0: there is no averaged model to evaluate")
         self.optimizer = AvAdam([
             {"params": list(self.visual_encoder.parameters()), "lr": learning_rate},
             {"params": list(self.audio_encoder.parameters()), "lr": 2e-5},
             {"params": list(self.fusion_module.parameters()), "lr": learning_rate},
             {"params": list(self.decoder1.parameters()), "lr": learning_rate},
-        ], max_grad_norm=max_grad_norm, warmup_steps=warmup_steps, total_steps=total_steps)     # ValueError on bad values
+        ], max_grad_norm=max_grad_norm, warmup_steps=warmup_steps, total_steps=total_steps, ema_decay=ema_decay,
+            ema_warmup=ema_warmup)                                                          # ValueError on bad values
         self.max_grad_norm, self.warmup_steps, self.total_steps = max_grad_norm, warmup_steps, total_steps
+        self.ema_decay, self.ema_warmup = ema_decay, ema_warmup
         # model/trainer.py:40 (GradScaler); off by default: bf16 operands need no loss scaling.  On = the reference's overflow-skip /
         # growth / backoff law, evaluated on the device
         self.scaler = AvGradScaler(device=device, enabled=loss_scaling)
@@ -502,8 +516,15 @@ class MultimodalTrainer:
             prev = idx
         return result
 
-    @torch.no_grad()
     def evaluate(self, dataloader):
+        """(loss, WER) over the loader.  With ``eval_ema`` the loop runs on the averaged weights and the trained ones are back afterwards."""
+        if self.eval_ema:
+            with self.optimizer.averaged():
+                return self._evaluate(dataloader)
+        return self._evaluate(dataloader)
+
+    @torch.no_grad()
+    def _evaluate(self, dataloader):
         self.visual_encoder.eval(); self.audio_encoder.eval(); self.fusion_module.eval(); self.decoder1.eval()
         refs1, hyps1, refs2, hyps2 = [], [], [], []
         total_loss = 0.0
@@ -568,8 +589,15 @@ class MultimodalTrainer:
         self.last_report = {"speaker1": rates(acc[0]), "speaker2": rates(acc[1])}
         return self.last_report["speaker1"]["word"]["rate"], self.last_report["speaker2"]["word"]["rate"]
 
-    @torch.no_grad()
     def align(self, batch, frame_rate: float = 25.0):
+        """``_align`` - on the averaged weights with ``eval_ema``."""
+        if self.eval_ema:
+            with self.optimizer.averaged():
+                return self._align(batch, frame_rate)
+        return self._align(batch, frame_rate)
+
+    @torch.no_grad()
+    def _align(self, batch, frame_rate: float = 25.0):
         """Word times of both speakers' transcripts in one batch: CTC forced alignment (align.forced_align, csrc/ctc_align.hip) of
         ``text*`` against the log-probs of ONE forward_losses call in eval mode.  Returns (segments1, segments2): per utterance the
         ``align.word_segments`` list ([] for a transcript that cannot be aligned).  The CTC head runs at the lip-frame rate, so

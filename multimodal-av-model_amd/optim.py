@@ -3,8 +3,11 @@ model/trainer.py:34-39).  State keys (step / exp_avg / exp_avg_sq) match torch.o
 checkpoint dict (main.py:47-55) stays loadable.  ``grad_scale`` folds the data-parallel 1/world_size (or a loss
 un-scale) into the step so that no extra pass over the gradients is needed.  Opt-in (``max_grad_norm`` / ``warmup_steps`` /
 ``total_steps``): global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, decided on the device inside
-the same fused step."""
+the same fused step.  Opt-in (``ema_decay``): an exponential moving average of the weights kept by that step, and
+``swap_averaged`` / ``averaged`` to evaluate and save with it."""
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
@@ -80,10 +83,32 @@ def check_clip_schedule(max_grad_norm, warmup_steps, total_steps):
     return max_grad_norm, warmup_steps, total_steps
 
 
+def ema_decay(k: int, decay: float, warmup: bool = False) -> float:
+    """Decay d_k of EMA update ``k`` (0-based, counting updates actually made), in float64: d_0 = 0 - the first update copies the
+    parameters, torch.optim.swa_utils.AveragedModel's ``n_averaged == 0`` - then ``decay``, or min(decay, (1 + k) / (10 + k)) with
+    ``warmup`` (TensorFlow's ExponentialMovingAverage, timm's ModelEmaV2).  The update is ``torch.lerp(ema, p_new, 1 - d_k)``.  The host form
+    of the law the fused step evaluates on the device (tests, logging)."""
+    k, decay = int(k), float(decay)
+    if k < 1:
+        return 0.0
+    return min(decay, (1.0 + k) / (10.0 + k)) if warmup else decay
+
+
+def check_ema(decay, warmup=False):
+    """Validated (ema_decay, ema_warmup); ValueError otherwise (the conditions of av_adam_multi_ema).  0 = no EMA."""
+    decay, warmup = float(decay), bool(warmup)
+    if not 0.0 <= decay < 1.0:                                  # NaN fails both comparisons
+        raise ValueError(f"ema_decay must be in [0, 1) (0 = no EMA), got {decay}")
+    return decay, warmup
+
+
 class _Plan:
     """Static part of one multi-tensor launch (cached per set of (parameter, hyper-parameters)): sizes, {lr, beta1, beta2, eps} per tensor,
     chunk table, step-table slots - and the pointer table of its last launch (re-uploaded only when a pointer changed)."""
-    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptr_list", "ptr_host", "ptr_dev", "ptr_evt")
+    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptr_list", "ptr_host", "ptr_dev", "ptr_evt",
+                 # with an EMA: sizes and chunk table of the "EMA-only" tensors (an average, no gradient in this pattern) and the EMA pointer table
+                 # [n] + [n_only][2], kept like the pointer table above
+                 "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema_list", "ema_host", "ema_dev", "ema_evt")
 
 
 class AvAdam(torch.optim.Optimizer):
@@ -96,13 +121,26 @@ class AvAdam(torch.optim.Optimizer):
     the step sees them: times ``grad_scale``, un-scaled under loss scaling); ``warmup_steps`` / ``total_steps`` scale every group's ``lr``
     by ``lr_multiplier(k)``, k = steps actually taken.  Both are evaluated on the device by ``av_adam_multi_ex`` (one more read of the
     gradients for the norm; no host synchronisation, no new plan); ``param_groups[i]["lr"]`` stays the base rate.  All off (the default):
-    the step is ``av_adam_multi``, as before."""
+    the step is ``av_adam_multi``, as before.
+
+    ``ema_decay`` > 0 keeps ``state[p]["ema"]`` (fp32, created as a copy of ``p`` at the first step in which ``p`` has a gradient; a
+    parameter that never gets one has no average: its averaged value is itself): every non-skipped step moves it by
+    ``torch.lerp(ema, p_new, 1 - ema_decay(k))`` inside the Adam launch (``av_adam_multi_ema``), parameters without a gradient in that step
+    included; under loss scaling the device skips it with the step.  ``swap_averaged()`` / ``averaged()`` exchange parameters and averages in
+    place, 16-bit shadows included.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated."""
 
     SCHEDULE_KEY = "av_schedule_step"     # state_dict entry of the schedule step; torch.optim.Adam.load_state_dict ignores it
+    EMA_KEY = "av_ema_step"               # ... of the count of EMA updates
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, warmup_steps=0, total_steps=0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, warmup_steps=0, total_steps=0, ema_decay=0.0,
+                 ema_warmup=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.max_grad_norm, self.warmup_steps, self.total_steps = check_clip_schedule(max_grad_norm, warmup_steps, total_steps)
+        self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
+        self._ema_state = None        # device block {decay of the last update, count of updates}, made by the first step
+        self._ema_seed = 0            # count to put into a fresh block (load_state_dict)
+        self._swapped = False         # swap_averaged(): the parameters currently hold the averages
+        self._swap_plan = None
         self._clip_state = None       # device block {norm, clip coefficient, lr multiplier, schedule step}, made by the first step
         self._clip_ws = None          # one double per chunk of all parameters
         self._sched_seed = 0          # schedule step to put into a fresh block (load_state_dict)
@@ -193,9 +231,81 @@ class AvAdam(torch.optim.Optimizer):
         if self._clip_state is not None:
             self._clip_state.view(torch.int32)[3:4].fill_(self._sched_seed)
 
+    @property
+    def averaging(self) -> bool:
+        return self.ema_decay > 0.0
+
+    def _ema_block(self, dev):
+        if self._ema_state is None or self._ema_state.device != torch.device(dev):
+            self._ema_state = torch.zeros(2, dtype=torch.float32, device=dev)
+            if self._ema_seed:
+                self._ema_state.view(torch.int32)[1:2].fill_(self._ema_seed)
+        return self._ema_state
+
+    @property
+    def last_ema_decay(self):
+        """0-dim device tensor (a view of the EMA state block, no sync): decay d_k the last step's EMA update ran at.  None before the
+        first step with an EMA."""
+        return None if self._ema_state is None else self._ema_state[0]
+
+    def ema_step(self) -> int:
+        """EMA updates made so far (synchronises with the device, like schedule_step)."""
+        if self._ema_state is None:
+            return self._ema_seed
+        return int(self._ema_state.view(torch.int32)[1])
+
+    def _set_ema_step(self, k: int) -> None:
+        self._ema_seed = int(k)
+        if self._ema_state is not None:
+            self._ema_state.view(torch.int32)[1:2].fill_(self._ema_seed)
+
+    def _averaged_params(self):
+        return [p for group in self.param_groups for p in group["params"] if "ema" in self.state.get(p, ())]
+
+    @torch.no_grad()
+    def swap_averaged(self) -> None:
+        """Exchange every parameter that has an average with it, in place, in one launch (av_param_swap_multi): afterwards the model
+        computes with the averaged weights and ``state[p]["ema"]`` holds the trained ones; a second call swaps back, bit for bit.  The
+        16-bit shadows of those parameters are written by the same launch and every other compute-dtype cache rebuilds.  Parameters
+        without an average stay as they are.  ``step()`` refuses to run in between."""
+        ps = self._averaged_params()
+        self._swapped = not self._swapped
+        if not ps:
+            return
+        import numpy as np
+        dev = ps[0].device
+        shadows = shadow.lookup_many(ps)
+        flat = []
+        for p, sh in zip(ps, shadows):
+            flat += [p.data_ptr(), self.state[p]["ema"].data_ptr(), sh.data_ptr() if sh is not None else 0]
+        key = (tuple(flat), tuple(p.numel() for p in ps))
+        if self._swap_plan is None or self._swap_plan[0] != key:
+            ct, cs = [], []
+            for t, p in enumerate(ps):
+                for s0 in range(0, p.numel(), self.CHUNK):
+                    ct.append(t); cs.append(s0)
+            self._swap_plan = (key, ops.h2d_async(np.asarray(flat, dtype=np.int64), dev),
+                               ops.h2d_async(np.asarray([p.numel() for p in ps], dtype=np.int64), dev),
+                               ops.h2d_async(np.asarray(ct, dtype=np.int32), dev), ops.h2d_async(np.asarray(cs, dtype=np.int64), dev), len(ct))
+        _, ptrs, sizes, ct, cs, nch = self._swap_plan
+        L.check(L.lib().av_param_swap_multi(ops.ptr(ptrs), ops.ptr(sizes), ops.ptr(ct), ops.ptr(cs), nch, self.CHUNK, ops.stream()),
+                "av_param_swap_multi")
+        torch.autograd.graph.increment_version(ps)              # compute-dtype caches (re-layouts) rebuild
+        shadow.mark_fresh([p for p, sh in zip(ps, shadows) if sh is not None])          # ... the shadows were just written
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with optimizer.averaged():`` - the model holds the averaged weights inside the block and the trained ones after it."""
+        self.swap_averaged()
+        try:
+            yield self
+        finally:
+            self.swap_averaged()
+
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._set_schedule_step(state_dict.get(self.SCHEDULE_KEY, 0))
+        self._set_ema_step(state_dict.get(self.EMA_KEY, 0))
         for st in self.state.values():                              # torch >= 2 stores 'step' as a tensor in its own checkpoints
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"])
@@ -207,15 +317,20 @@ class AvAdam(torch.optim.Optimizer):
         self._steps_seeded = False
         self._keep = None
         self._set_schedule_step(0)
+        self._set_ema_step(0)
+        self._swapped = False
 
     def state_dict(self):
         """torch.optim.Adam's format.  Under loss scaling only the device table knows the per-parameter step counts (overflowing steps are
         skipped on the device): bring the host entries up to date first, so that a checkpoint taken through this method - not only through
-        ``checkpoint_dict`` - resumes with the right bias corrections.  With a schedule the dict also carries its step (SCHEDULE_KEY)."""
+        ``checkpoint_dict`` - resumes with the right bias corrections.  With a schedule the dict also carries its step (SCHEDULE_KEY), with an EMA
+        the count of its updates (EMA_KEY) beside the ``ema`` tensors of the per-parameter state."""
         self.sync_steps()
         sd = super().state_dict()
         if self.scheduled:
             sd[self.SCHEDULE_KEY] = self.schedule_step()
+        if self.averaging:
+            sd[self.EMA_KEY] = self.ema_step()
         return sd
 
     def add_param_group(self, param_group):
@@ -228,9 +343,11 @@ class AvAdam(torch.optim.Optimizer):
         self._plans = {}
         self._clip_ws = None                                        # sized by the chunks of all parameters
 
-    def _plan(self, plist, dev) -> _Plan:
+    def _plan(self, plist, dev, ema_only=None) -> _Plan:
         slots = self._slots()
         key = tuple((p.data_ptr(), p.numel(), hp, slots[id(p)]) for p, hp, _ in plist)
+        if ema_only is not None:                                    # with an EMA the tensors WITHOUT a gradient are part of the pattern
+            key = (key, tuple((p.data_ptr(), p.numel()) for p in ema_only))
         pl = self._plans.get(key)
         if pl is None:
             import numpy as np
@@ -250,6 +367,20 @@ class AvAdam(torch.optim.Optimizer):
             pl.ptr_list = pl.ptr_evt = None
             pl.ptr_host = torch.empty(5 * len(plist), dtype=torch.long).pin_memory()
             pl.ptr_dev = torch.empty(5 * len(plist), dtype=torch.long, device=dev)
+            if ema_only is not None:
+                ct, cs = [], []
+                for t, p in enumerate(ema_only):
+                    for s0 in range(0, p.numel(), self.CHUNK):
+                        ct.append(t); cs.append(s0)
+                pl.eo_n, pl.eo_nch = len(ema_only), len(ct)
+                pl.eo_sizes = pl.eo_ct = pl.eo_cs = None
+                if ema_only:
+                    pl.eo_sizes = ops.h2d_async(np.asarray([p.numel() for p in ema_only], dtype=np.int64), dev)
+                    pl.eo_ct = ops.h2d_async(np.asarray(ct, dtype=np.int32), dev)
+                    pl.eo_cs = ops.h2d_async(np.asarray(cs, dtype=np.int64), dev)
+                pl.ema_list = pl.ema_evt = None
+                pl.ema_host = torch.empty(len(plist) + 2 * len(ema_only), dtype=torch.long).pin_memory()
+                pl.ema_dev = torch.empty(len(plist) + 2 * len(ema_only), dtype=torch.long, device=dev)
             self._plans[key] = pl
         return pl
 
@@ -269,13 +400,18 @@ class AvAdam(torch.optim.Optimizer):
 
     def step(self, closure=None, scaler: "AvGradScaler" = None):
         """One fused multi-tensor launch for all parameters that have a gradient (per-tensor step counts, per-group lr / betas / eps)."""
+        if self._swapped:
+            raise RuntimeError("AvAdam.step: the parameters hold the averaged weights (swap_averaged); swap back before stepping")
         loss = closure() if closure is not None else None
         plist = []
+        ema_only = [] if self.averaging else None                   # an average, no gradient in this step: still moved towards p
         for group in self.param_groups:
             b1, b2 = group["betas"]
             hp = (float(group["lr"]), float(b1), float(b2), float(group["eps"]))
             for p in group["params"]:
                 if p.grad is None:
+                    if ema_only is not None and "ema" in self.state.get(p, ()):
+                        ema_only.append(p)
                     continue
                 if not p.is_cuda or p.dtype != torch.float32:
                     raise RuntimeError("AvAdam: parameters must be float32 CUDA tensors (no CPU fallback)")
@@ -284,12 +420,14 @@ class AvAdam(torch.optim.Optimizer):
                     state["step"] = 0
                     state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if ema_only is not None and "ema" not in state:
+                    state["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
                 plist.append((p, hp, state))
         if not plist:
             return loss
         dev = plist[0][0].device
         steps = self._step_table(dev)                               # BEFORE the host counts move: a fresh table is seeded from them
-        pl = self._plan(plist, dev)
+        pl = self._plan(plist, dev, ema_only)
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p, _, _ in plist]
         shadows = shadow.lookup_many([p for p, _, _ in plist])  # bf16 compute copies (perf path), written by the kernel
         flat = []
@@ -308,7 +446,24 @@ class AvAdam(torch.optim.Optimizer):
             args += [ops.ptr(scaler.state), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval]
         else:
             args += [None, 1.0, 1.0, 1]
-        if self.clipping or self.scheduled:
+        if self.averaging:
+            eflat = [st["ema"].data_ptr() for _, _, st in plist]
+            for p in ema_only:
+                eflat += [p.data_ptr(), self.state[p]["ema"].data_ptr()]
+            if pl.ema_list != eflat:
+                if pl.ema_evt is not None:
+                    pl.ema_evt.synchronize()
+                pl.ema_host.copy_(torch.tensor(eflat, dtype=torch.long))
+                pl.ema_dev.copy_(pl.ema_host, non_blocking=True)
+                pl.ema_evt = torch.cuda.Event(); pl.ema_evt.record()
+                pl.ema_list = eflat
+            cstate, ws = self._clip_block(dev) if self.clipping or self.scheduled else (None, None)
+            only = pl.ema_dev.data_ptr() + 8 * pl.n if pl.eo_n else None
+            L.check(L.lib().av_adam_multi_ema(*args, self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
+                                              ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), ops.ptr(pl.ema_dev),
+                                              only, ops.ptr(pl.eo_sizes), ops.ptr(pl.eo_ct), ops.ptr(pl.eo_cs), pl.eo_nch, self.ema_decay,
+                                              int(self.ema_warmup), ops.ptr(self._ema_block(dev)), ops.stream()), "av_adam_multi_ema")
+        elif self.clipping or self.scheduled:
             cstate, ws = self._clip_block(dev)
             L.check(L.lib().av_adam_multi_ex(*args, self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
                                              ws.numel() * ws.element_size(), ops.ptr(cstate), ops.stream()), "av_adam_multi_ex")
