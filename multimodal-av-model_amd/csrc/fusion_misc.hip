@@ -51,6 +51,7 @@ __global__ __launch_bounds__(256) void compact_kernel(const long long* __restric
 struct LerpCoef { int i0, i1; float lam; };
 __device__ __forceinline__ LerpCoef lerp_coef(int i, int Tm, int Tv) {
     LerpCoef c;
+    if (Tm <= 0) { c.i0 = -1; c.i1 = -1; c.lam = 0.f; return c; }         // a group without a speech frame: no source frame exists
     if (Tm == Tv) { c.i0 = i; c.i1 = i; c.lam = 0.f; return c; }          // no interpolation (fusion_module.py:50)
     const float scale = Tv > 1 ? (float)(Tm - 1) / (float)(Tv - 1) : 0.f;  // align_corners=True
     const float src = scale * (float)i;
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void gather_lerp_fwd_kernel(const float* __res
     const int i = blockIdx.x, b = blockIdx.y;
     const int Tm = tmax[b / gsize], n = cnt[b];
     const LerpCoef c = lerp_coef(i, Tm, Tv);
-    const bool ok0 = c.i0 < n, ok1 = c.i1 < n;
+    const bool ok0 = c.i0 >= 0 && c.i0 < n, ok1 = c.i1 >= 0 && c.i1 < n;    // an index below 0 (Tm = 0) reads nothing: zero rows, mask 0, length 0
     const float* r0 = ok0 ? feat + ((long long)b * Ta + idx[(long long)b * Ta + c.i0]) * D : nullptr;
     const float* r1 = ok1 ? feat + ((long long)b * Ta + idx[(long long)b * Ta + c.i1]) * D : nullptr;
     float* o = out + ((long long)b * Tv + i) * D;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void gather_lerp_fwd_kernel(const float* __res
             j = (int)floorf((float)i * ((float)Tm / (float)Tv));
             if (j > Tm - 1) j = Tm - 1;
         }
-        const long long mv = j < n ? mask[(long long)b * Ta + idx[(long long)b * Ta + j]] : 0;
+        const long long mv = j >= 0 && j < n ? mask[(long long)b * Ta + idx[(long long)b * Ta + j]] : 0;
         mout[(long long)b * Tv + i] = mv;
         if (mv != 0) atomicAdd(lens + b, 1ull);
     }
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void gather_lerp_bwd_kernel(const float* __res
                                                               float* __restrict__ dfeat, int Ta, int Tv, int D, int gsize) {
     const int j = blockIdx.x, b = blockIdx.y;
     const int Tm = tmax[b / gsize], n = cnt[b];
-    if (j >= n) return;
+    if (Tm <= 0 || j >= n) return;                            // no speech frame in the group: dfeat stays zero
     int lo, hi;
     if (Tm == Tv) { lo = j; hi = j; }
     else {
