@@ -436,6 +436,36 @@ int av_error_counts(const int* ref_ids, long long ref_ld, const long long* ref_l
                     long long hyp_ld_n, const long long* hyp_lens, int B, int N, int Lr, int Lh, int ref_skip_id, int hyp_skip_id,
                     const int* piece_offsets, const int* piece_chars, int V, int max_piece, int* out_counts, void* workspace,
                     long long workspace_bytes, void* stream);
+/* Training-time augmentation on the device (csrc/augment.hip; augment.py restates both laws on the host bit for bit).
+ * Every random choice is a draw of the dropout generator (drop_draw of csrc/av_common.h), a pure function of (seed, stream, block): a
+ * block yields four 16-bit integers k0..k3, an integer in 0..R-1 is (k * R) >> 16.  Clip b at step `step` has the counter
+ * c = step * 65536 + b (b < 65536, 0 <= step < 2^24).  Nothing synchronises, nothing is drawn on the host.
+ * av_augment_lips: src, dst fp32 [B][T][H][W] (the [B][1][T][H][W] view of the trainer is the same bytes), out of place (src == dst or an
+ *   overlap is an error status); lengths int64 [B] on the device or NULL (= T), clamped to [0, T].
+ *     dst[b][t][y][x] = src[b][tsrc(t)][clamp(y - dy, 0, H-1)][clamp((flip ? W-1-x : x) - dx, 0, W-1)],  0 for t >= lengths[b] (not read)
+ *   block c * 64 + 0 of stream_id: dx = draw(k0, 2 S + 1) - S, dy = draw(k1, 2 S + 1) - S with S = max_shift < min(H, W),
+ *     flip = k2 < flip_thr (flip_thr = ceil(65536 p) in [0, 65536]).
+ *   frame freeze (dropped video frames): segment j = 0 .. ceil(n / E) - 1 of the n valid frames (E = mask_every >= 1) takes k[2 (j % 2)] and
+ *     k[2 (j % 2) + 1] of block c * 64 + 1 + j / 2: s_j = draw(., E), w_j = draw(., mask_max + 1), span_j = [j E + s_j, min(j E + s_j + w_j, n)).
+ *     0 <= mask_max <= E and ceil(T / E) <= 126, so a frame lies at most in its own segment's span and the previous one's; inside a span
+ *     it reads input frame max(start - 1, 0) (the own segment's span wins), every other frame reads itself; freezes do not chain.
+ *   Nothing is computed in floating point.  max_shift = flip_thr = mask_max = 0 is a copy.
+ * av_augment_noise: x, y fp32 [B][N] (N <= 2^24; y may be x), lengths int64 [B] = valid samples (required), clamped to [0, N].
+ *   P_b = mean of x^2 over the valid samples, in double, fixed order, no atomics (the same bits on every run);
+ *   snr_b = fl(snr_lo + fl(u fl(snr_hi - snr_lo))) in fp32, u = k0 / 65536 of block c of AV_AUG_STREAM_SNR;
+ *   sigma_b = (float)sqrt(P_b 10^(-snr_b / 10)) in double -> sigma_out[b];  0 for P_b = 0 or no valid sample: that row is copied.
+ *   y[b][i] = fl(x + fl(sigma_b z_i)) for i < lengths[b], x beyond;  z_i = (float)(k0 + k1 + k2 + k3 - 131070) * fp32(1 / sqrt((65536^2 - 1) / 3))
+ *   from block (c << 24) + i of AV_AUG_STREAM_NOISE: zero mean, unit variance, |z| <= 3.47, exact in integers.
+ *   power_ws: B * (1 + ceil(N / AV_AUG_NOISE_CHUNK)) doubles (at least 2 B), 8-byte aligned; P_b is left in power_ws[b]. */
+#define AV_AUG_STREAM_LIP1 0xF0000011u
+#define AV_AUG_STREAM_LIP2 0xF0000012u
+#define AV_AUG_STREAM_SNR 0xF0000013u
+#define AV_AUG_STREAM_NOISE 0xF0000014u
+#define AV_AUG_NOISE_CHUNK 8192
+int av_augment_lips(const float* src, float* dst, const long long* lengths, int B, int T, int H, int W, unsigned long long seed,
+                    long long step, unsigned stream_id, int max_shift, int flip_thr, int mask_max, int mask_every, void* stream);
+int av_augment_noise(const float* x, float* y, const long long* lengths, int B, int N, unsigned long long seed, long long step,
+                     float snr_lo, float snr_hi, double* power_ws, float* sigma_out, void* stream);
 /* device side of the input pipeline (dataset/multi_speaker_dataset.py:13-59; decoding wav / npy files stays on the host):
  * av_lip_gray_resize: src [T][Hs][Ws][C] (uint8 if src_is_u8 else fp32) -> dst fp32 [T][Hd][Wd] = bilinear(mean over C) / divisor
  *   (:49-58: .astype(float32).mean(-1), cv2.resize INTER_LINEAR law, / 255), float32 operation order of the reference;

@@ -144,6 +144,8 @@ SIGNATURES = {
     "av_ctc_align": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, ll, vp],
     "av_error_counts_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(ll)],
     "av_error_counts": [vp, ll, vp, vp, ll, ll, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, ll, vp],
+    "av_augment_lips": [vp, vp, vp, i32, i32, i32, i32, C.c_ulonglong, ll, C.c_uint, i32, i32, i32, i32, vp],
+    "av_augment_noise": [vp, vp, vp, i32, i32, C.c_ulonglong, ll, f32, f32, vp, vp, vp],
     "av_lip_gray_resize": [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp],
     "av_mix_pair": [vp, ll, vp, ll, vp, vp, vp, vp, vp],
     "av_adam_multi": [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, f32, vp, f32, f32, i32, vp],

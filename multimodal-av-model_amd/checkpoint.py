@@ -1,6 +1,7 @@
 """Checkpoint helpers with the reference's dict layout (main.py:47-64): ``epoch`` + four module state_dicts (the reference's key
 sets: visual 129, audio 422, fusion 30, decoder 2) + the optimizer state (torch-Adam keys), so a file written by either side
-loads on the other.  Loading never unpickles code: ``torch.load(..., weights_only=True)``."""
+loads on the other.  Optional entries beside them, written only when the feature is on and ignored by the reference: ``scaler`` (loss
+scaling) and ``augment`` (augment.Augment: step and seed as plain ints).  Loading never unpickles code: ``torch.load(..., weights_only=True)``."""
 from __future__ import annotations
 
 import torch
@@ -16,6 +17,9 @@ def checkpoint_dict(epoch: int, trainer, averaged: bool = False) -> dict:
     if sc is not None and sc.enabled:
         trainer.optimizer.sync_steps(sc)             # steps actually taken (overflowing steps are skipped on the device)
     extra = {"scaler": sc.state_dict()} if sc is not None and sc.enabled else {}
+    aug = getattr(trainer, "augment", None)
+    if aug is not None:
+        extra["augment"] = aug.state_dict()          # plain ints (step, seed): the resumed run draws the plans the uninterrupted one would
     opt = trainer.optimizer.state_dict()
     mods = (("visual_encoder", trainer.visual_encoder), ("audio_encoder", trainer.audio_encoder), ("fusion", trainer.fusion_module),
             ("decoder1", trainer.decoder1))
@@ -51,4 +55,7 @@ def load_checkpoint(trainer, path: str, *, audio_encoder: bool = False, optimize
         sc = getattr(trainer, "scaler", None)
         if sc is not None and sc.enabled and "scaler" in ck:
             sc.load_state_dict(ck["scaler"])                     # (AvAdam.load_state_dict re-seeds the device-side per-parameter step table)
+        aug = getattr(trainer, "augment", None)
+        if aug is not None and "augment" in ck:
+            aug.load_state_dict(ck["augment"])
     return int(ck["epoch"]) + 1

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from .. import ops
 from .. import _lib as L
 from ..align import forced_align, word_segments
+from ..augment import Augment
 from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
 from ..bias import ContextBias
 from ..lm import NGramLM
@@ -82,7 +83,7 @@ class MultimodalTrainer:
                  eval_bias_weight: Optional[float] = None, mwer_weight: Optional[float] = None, mwer_nbest: Optional[int] = None,
                  mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
-                 ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None):
+                 ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None):
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -148,6 +149,16 @@ class MultimodalTrainer:
         if mwer_level not in ("word", "char", "token"):
             raise ValueError(f"mwer_level must be 'word', 'char' or 'token', got {mwer_level!r}")
         self._mwer_table = None                                # the tokenizer's PieceTable, built once when the term first runs
+        # opt-in: data augmentation on the device (augment.Augment, csrc/augment.hip): in a training step forward_losses feeds the encoders
+        # shifted / mirrored / frame-frozen lip clips and the mixture with noise at a drawn SNR, written into buffers this trainer owns (the
+        # batch's tensors are never written).  augment: an Augment; None reads AVAMD_AUG_SHIFT / _FLIP / _TMASK / _TMASK_EVERY / _SNR / _SEED
+        # (augment.Augment.from_env: nothing set = off).  evaluate() and align() never augment.  Off: none of that code runs and no buffer
+        # exists.  Data parallel: each rank adds its rank to the seed, as the dropout generator does
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError(f"augment must be an augment.Augment or None, got {type(augment).__name__}")
+        self.augment = Augment.from_env() if augment is None else augment
+        self._aug_buf = {}
+        self.last_aug_sigma = None                             # noise level per item of the last augmented step, device float32 [B]
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         # opt-in: global-norm gradient clipping and a linear warmup / decay of the learning rate inside the fused Adam step (optim.AvAdam,
@@ -198,6 +209,8 @@ class MultimodalTrainer:
                 m = self.audio_encoder.model
                 m.layerdrop_generator = torch.Generator().manual_seed(0x5EED1A7E)
                 m.dropout_generator = torch.Generator().manual_seed(0xD120 + 7919 * dist.get_rank(reducer.group))
+                if self.augment is not None:
+                    self.augment.rank_offset = dist.get_rank(reducer.group)
             self.audio_encoder.model.grad_ready = reducer.reduce_async
             self.audio_encoder.model.grad_flat_ready = reducer.reduce_flat
             self.audio_encoder.model.grad_wait = reducer.wait
@@ -280,6 +293,8 @@ class MultimodalTrainer:
         if self.native_ctc:
             self.fusion_module.finish_flag_check(wait=True)        # staged one step ago: its event has completed unless the host runs far ahead
         d = self._to_dev(batch)
+        if self.augment is not None and torch.is_grad_enabled() and self.decoder1.training and self.audio_encoder.training:
+            self._augment_inputs(d, batch)                         # on the main stream, before the lip streams fork
         use_side = self.visual_side_stream and d["audio"].is_cuda
         if use_side:
             # the frozen visual encoder runs beside the wav2vec2 forward, one stream per speaker: its HBM-bound BatchNorm / pooling passes overlap
@@ -423,6 +438,29 @@ class MultimodalTrainer:
                    input_lengths2=il2, log_probs1=lp1, log_probs2=lp2, loss1=l1, loss2=l2, contrast1=c1, contrast2=c2, total=total)
         return out
 
+    def _aug_buffer(self, name: str, like: torch.Tensor) -> torch.Tensor:
+        buf = self._aug_buf.get(name)
+        if buf is None or buf.shape != like.shape or buf.device != like.device:
+            buf = self._aug_buf[name] = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+        return buf
+
+    def _augment_inputs(self, d, batch) -> None:
+        """Replaces d["lip1"], d["lip2"] and d["audio"] by their augmented versions of step ``augment.step``, in buffers reused from step to
+        step (the previous step's readers have finished in stream order: the lip streams are joined before the fusion).  Valid lengths stay
+        on the device; nothing synchronises."""
+        aug = self.augment
+        if aug.lips_on:
+            for spk in (1, 2):
+                key = f"lip{spk}"
+                d[key] = aug.lips(d[key], batch.get(key + "_lengths"), aug.step, spk, out=self._aug_buffer(key, d[key]))
+        if aug.noise_on:
+            B = d["audio"].shape[0]
+            sg = self._aug_buf.get("sigma")
+            if sg is None or sg.shape[0] != B or sg.device != d["audio"].device:
+                sg = self._aug_buf["sigma"] = torch.empty((B,), dtype=torch.float32, device=d["audio"].device)
+            d["audio"], self.last_aug_sigma = aug.noise(d["audio"], (d["mask1"] != 3).sum(1), aug.step,
+                                                        out=self._aug_buffer("audio", d["audio"]), sigma=sg)
+
     def _mwer(self, lp, refs, ref_lengths, input_lengths):
         """Per-utterance MWER risk [B] of one decoder call (mwer.mwer_loss, reduction "none"); float32 log-probs as the CTC loss reads them."""
         from ..mwer import mwer_loss
@@ -443,6 +481,8 @@ class MultimodalTrainer:
         if self.reducer is not None:
             self._head_done = False
         out = self.forward_losses(batch)
+        if self.augment is not None:
+            self.augment.step += 1                                 # once per training step: the next step draws a new plan
         self.scaler.scale(out["total"]).backward()                 # model/trainer.py:121
         self._head_arena.finalize()
         if self.reducer is not None:
