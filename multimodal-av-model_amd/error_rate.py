@@ -32,6 +32,22 @@ _INS, _DEL, _SUB = 1 << 32, (1 << 32) | 1, (1 << 32) | (1 << 16)
 _SPACE, _META_SPACE = 0x20, 0x2581
 
 
+def word_error_rate(refs, hyps) -> float:
+    """jiwer.wer stand-in (jiwer is not installed): total word-level edit distance / total reference words."""
+    errs = words = 0
+    for r, h in zip(refs, hyps):
+        r, h = r.split(), h.split()
+        prev = list(range(len(h) + 1))
+        for i in range(1, len(r) + 1):
+            cur = [i] + [0] * len(h)
+            for j in range(1, len(h) + 1):
+                cur[j] = min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (r[i - 1] != h[j - 1]))
+            prev = cur
+        errs += prev[-1]
+        words += len(r)
+    return errs / max(1, words)
+
+
 class PieceTable:
     """The tokenizer's pieces as code points: ``offsets`` int32 [V + 1], ``chars`` int32 [offsets[V]] (piece i = chars[offsets[i] :
     offsets[i + 1]]), ``max_piece`` the longest piece; ``on(device)`` is the cached device copy."""

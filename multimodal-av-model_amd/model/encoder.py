@@ -368,3 +368,25 @@ class VisualEncoder(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("the HIP visual encoder is forward-only: freeze trunk and frontend3D as main.py:100-103 does")
         return self._forward_impl(x)
+
+    def forward_pair(self, lip1, lip2, streams):
+        """``forward(lip1)`` on streams[0] and ``forward(lip2)`` on streams[1], both forked from the current stream -> (feat1, feat2); the caller
+        joins the streams.  Two different streams: the BatchNorm running statistics are still updated in call order (``_bn``: the leading call
+        records an event behind each finalize kernel, the following call waits for it).  One stream twice: two plain calls on it."""
+        (s1, s2), main = streams, torch.cuda.current_stream(lip1.device)
+        two, evs = s2 is not s1, []
+        self.warm_caches(compute_dtype())                      # weight re-layouts are built on main, before the lip streams fork
+        s1.wait_stream(main)
+        try:
+            with torch.cuda.stream(s1):
+                if two:
+                    self._bn_sync, self._bn_idx = ("lead", evs), 0
+                f1 = self(lip1)
+            if two:
+                s2.wait_stream(main)
+                self._bn_sync, self._bn_idx = ("follow", evs), 0
+            with torch.cuda.stream(s2):
+                f2 = self(lip2)
+        finally:
+            self._bn_sync = None
+        return f1, f2

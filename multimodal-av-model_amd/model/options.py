@@ -1,0 +1,75 @@
+"""The opt-in settings of MultimodalTrainer in one table: keyword argument -> (environment variable, parser of its text, default text, cast of an
+explicit argument).  ``resolve(name, argument)``: an argument that is not None wins, otherwise the variable is parsed,
+otherwise the default text is.  The variables are read when the trainer is constructed.  Every feature is off at its default, and off means that
+none of its code runs.  Not here: AVAMD_AUG_* (augment.Augment.from_env), AVAMD_FUSED_LOSS / AVAMD_VISUAL_STREAMS (read when trainer.py is imported).
+"""
+from __future__ import annotations
+
+import os
+
+from .. import ops
+
+_is1 = lambda text: text == "1"         # noqa: E731  the flags that are on only at "1"
+_path = lambda text: text or None       # noqa: E731  an empty variable is an unset one
+_same = lambda x: x                     # noqa: E731
+
+OPTIONS = {
+    # CTC loss of forward_losses (and so of evaluate()) on the device kernels of ops.ctc_loss: lengths and targets stay on the device, the step holds
+    # no synchronising call and ignores host_metadata()'s ``_ctc_*_lengths``.  The law (on unless "0") is ops.native_ctc_default's, as for CTCDecoder
+    "native_ctc": ("AVAMD_NATIVE_CTC", lambda _text: ops.native_ctc_default(), "0", bool),
+    # evaluate() decodes with beam_search.prefix_beam_search of this width; 0 = greedy, what the reference's simple_beam_search computes
+    "eval_beam_width": ("AVAMD_EVAL_BEAM", int, "0", int),
+    # ... with n-gram shallow fusion: an lm.NGramLM, or the path of an ARPA file whose tokens are the tokenizer's pieces
+    "eval_lm": ("AVAMD_EVAL_LM", _path, "", _same),
+    "eval_lm_weight": ("AVAMD_EVAL_LM_WEIGHT", float, "0.5", float),
+    "eval_token_bonus": ("AVAMD_EVAL_TOKEN_BONUS", float, "0.0", float),
+    # ... with contextual phrase biasing, with or without eval_lm: a bias.ContextBias, or the path of a phrase file (UTF-8, one phrase per line);
+    # the weight 1.0 is a setting, not a tuned value
+    "eval_bias": ("AVAMD_EVAL_BIAS", _path, "", _same),
+    "eval_bias_weight": ("AVAMD_EVAL_BIAS_WEIGHT", float, "1.0", float),
+    # evaluate() counts token / character / word errors with their S / D / I split on the device (error_rate.error_counts), leaves the rates in
+    # ``last_report`` and takes its WER from those counts
+    "eval_report": ("AVAMD_EVAL_REPORT", _is1, "0", bool),
+    # minimum word error rate training (mwer.mwer_loss, all on the device): with gradients enabled forward_losses adds
+    # mwer_weight * (mwer1 + mwer2) / 2 to ``total``; evaluate()'s loss stays the CTC loss
+    "mwer_weight": ("AVAMD_MWER_WEIGHT", float, "0", float),
+    "mwer_nbest": ("AVAMD_MWER_NBEST", int, "4", int),
+    "mwer_beam": ("AVAMD_MWER_BEAM", int, "8", int),
+    # global-norm clipping (clip_grad_norm_'s law) and a linear warmup / decay of the learning rate (optim.lr_multiplier, one multiplier for all
+    # groups; with a warmup the first step runs at 0, as LambdaLR does) inside the fused Adam step: no synchronising call.  Data parallel: the
+    # norm is taken after the all-reduce, over grad * grad_scale, so every rank computes the same bits
+    "max_grad_norm": ("AVAMD_CLIP_NORM", float, "0", float),
+    "warmup_steps": ("AVAMD_WARMUP_STEPS", int, "0", int),
+    "total_steps": ("AVAMD_TOTAL_STEPS", int, "0", int),
+    # an exponential moving average of the trainable weights inside the same fused step (skipped with an overflowing step, moved for LayerDrop-ped
+    # layers too); ema_warmup: optim.ema_decay's.  eval_ema: evaluate() and align() run on the averages (swapped in and back in place; BatchNorm
+    # buffers are not averaged, AveragedModel's default).  Data parallel: every rank computes the same averages, nothing is communicated
+    "ema_decay": ("AVAMD_EMA_DECAY", float, "0", float),
+    "ema_warmup": ("AVAMD_EMA_WARMUP", _is1, "0", bool),
+    "eval_ema": ("AVAMD_EVAL_EMA", _is1, "0", bool),
+}
+
+
+def resolve(name: str, argument):
+    env, parse, default, cast = OPTIONS[name]
+    return parse(os.environ.get(env, default)) if argument is None else cast(argument)
+
+
+# cross-field checks, one per feature group; the trainer calls each right after it has resolved the group
+def check_decode(beam_width: int, what: str, value, lacks: str) -> None:
+    if value is not None and beam_width == 0:
+        raise ValueError(f"{what} needs eval_beam_width > 0: the greedy decode has no {lacks}")
+
+
+def check_mwer(weight: float, nbest: int, beam: int, level: str) -> None:
+    if not 0.0 <= weight < float("inf"):                   # NaN fails both comparisons
+        raise ValueError(f"mwer_weight must be finite and >= 0, got {weight}")
+    if not 1 <= nbest <= beam <= 64:
+        raise ValueError(f"need 1 <= mwer_nbest <= mwer_beam <= 64, got mwer_nbest={nbest} mwer_beam={beam}")
+    if level not in ("word", "char", "token"):
+        raise ValueError(f"mwer_level must be 'word', 'char' or 'token', got {level!r}")
+
+
+def check_ema(eval_ema: bool, ema_decay: float) -> None:
+    if eval_ema and not ema_decay > 0:
+        raise ValueError("eval_ema needs ema_decay > 0: there is no averaged model to evaluate")

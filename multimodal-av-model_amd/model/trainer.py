@@ -12,6 +12,7 @@ Differences that do not change results:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -27,24 +28,10 @@ from ..beam_search import fast_decode, greedy_batch, prefix_beam_search
 from ..bias import ContextBias
 from ..lm import NGramLM
 from ..contrastive import contrastive_loss_with_mask
+from ..error_rate import PieceTable, error_counts, rates, word_error_rate
 from ..optim import AvAdam, AvGradScaler
 from ..parallel.dp import GradArena, GradBucketReducer
-
-
-def word_error_rate(refs, hyps) -> float:
-    """jiwer.wer stand-in (jiwer is not installed): total word-level edit distance / total reference words."""
-    errs = words = 0
-    for r, h in zip(refs, hyps):
-        r, h = r.split(), h.split()
-        prev = list(range(len(h) + 1))
-        for i in range(1, len(r) + 1):
-            cur = [i] + [0] * len(h)
-            for j in range(1, len(h) + 1):
-                cur[j] = min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (r[i - 1] != h[j - 1]))
-            prev = cur
-        errs += prev[-1]
-        words += len(r)
-    return errs / max(1, words)
+from . import host_meta, options
 
 
 _FUSED_LOSS = os.environ.get("AVAMD_FUSED_LOSS", "1") != "0"
@@ -84,6 +71,7 @@ class MultimodalTrainer:
                  mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
                  ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None):
+        """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
         self.fusion_module = fusion_module.to(device)
@@ -92,68 +80,22 @@ class MultimodalTrainer:
         self.device = device
         self.lambda_ = lambda_
         self.audio_passes = audio_passes
-        # both speakers go through fusion / BiLSTM / CTC head as ONE 2B batch (items are independent there, so results are
-        # identical; it halves the number of latency-bound LSTM step launches), and the frozen visual encoder runs on a
-        # side stream concurrently with the wav2vec2 forward
+        # both speakers go through fusion / BiLSTM / CTC head as ONE 2B batch (items are independent there, so results are identical; it halves the
+        # number of latency-bound LSTM step launches), and the frozen visual encoder runs on side streams concurrently with the wav2vec2 forward
         self.pair_batched = pair_batched
         self.visual_side_stream = visual_side_stream
         self._vstream = None
         self.ctc_loss = nn.CTCLoss(blank=tokenizer.blank_id, zero_infinity=True)       # stays on PyTorch-ROCm (the default)
-        # opt-in: the CTC loss of both branches of forward_losses (and so of evaluate()) on the device kernels of ops.ctc_loss.  None reads
-        # AVAMD_NATIVE_CTC (default "0") here.  Lengths and targets stay on the device: the step then holds no synchronising call and
-        # ignores the host copies ``_ctc_input_lengths`` / ``_ctc_target_lengths`` of host_metadata()
-        self.native_ctc = ops.native_ctc_default() if native_ctc is None else bool(native_ctc)
-        # opt-in: evaluate() decodes with CTC prefix beam search of this width (beam_search.prefix_beam_search, csrc/ctc_beam.hip).  None reads
-        # AVAMD_EVAL_BEAM (default "0") here; 0 = the greedy decode, which is what the reference's simple_beam_search computes
-        self.eval_beam_width = int(os.environ.get("AVAMD_EVAL_BEAM", "0")) if eval_beam_width is None else int(eval_beam_width)
-        if self.eval_beam_width < 0:
-            raise ValueError(f"eval_beam_width must be >= 0, got {self.eval_beam_width}")
-        # opt-in: the beam search of evaluate() with n-gram shallow fusion (lm.NGramLM over the tokenizer's ids, csrc/ctc_beam_lm.hip).  eval_lm:
-        # an NGramLM or the path of an ARPA file whose tokens are the tokenizer's pieces; None reads AVAMD_EVAL_LM (default: none),
-        # AVAMD_EVAL_LM_WEIGHT (0.5) and AVAMD_EVAL_TOKEN_BONUS (0.0).  Used only with eval_beam_width > 0
-        eval_lm = os.environ.get("AVAMD_EVAL_LM") or None if eval_lm is None else eval_lm
-        if isinstance(eval_lm, (str, os.PathLike)):
-            eval_lm = NGramLM.from_arpa(os.fspath(eval_lm), tokenizer.token_to_id, vocab_size=tokenizer.vocab_size, blank=tokenizer.blank_id)
-        self.eval_lm = eval_lm
-        self.eval_lm_weight = float(os.environ.get("AVAMD_EVAL_LM_WEIGHT", "0.5")) if eval_lm_weight is None else float(eval_lm_weight)
-        self.eval_token_bonus = float(os.environ.get("AVAMD_EVAL_TOKEN_BONUS", "0.0")) if eval_token_bonus is None else float(eval_token_bonus)
-        if self.eval_lm is not None and self.eval_beam_width == 0:
-            raise ValueError("eval_lm needs eval_beam_width > 0: the greedy decode has no language model")
-        # opt-in: the beam search of evaluate() with contextual phrase biasing (bias.ContextBias over the tokenizer's ids), with or without
-        # eval_lm.  eval_bias: a ContextBias or the path of a phrase file (UTF-8, one phrase per line); None reads AVAMD_EVAL_BIAS (default:
-        # none) and AVAMD_EVAL_BIAS_WEIGHT (1.0: a setting, not a tuned value).  Used only with eval_beam_width > 0; unset: none of that code runs
-        eval_bias = os.environ.get("AVAMD_EVAL_BIAS") or None if eval_bias is None else eval_bias
-        if isinstance(eval_bias, (str, os.PathLike)):
-            eval_bias = ContextBias.from_file(os.fspath(eval_bias), tokenizer)
-        self.eval_bias = eval_bias
-        self.eval_bias_weight = float(os.environ.get("AVAMD_EVAL_BIAS_WEIGHT", "1.0")) if eval_bias_weight is None else float(eval_bias_weight)
-        if self.eval_bias is not None and self.eval_beam_width == 0:
-            raise ValueError("eval_bias needs eval_beam_width > 0: the greedy decode has no phrase biasing")
-        # opt-in: evaluate() also counts token / character / word errors with their S / D / I split on the device (error_rate.error_counts,
-        # csrc/error_counts.hip), leaves the rates in ``last_report`` and takes its WER from those counts.  None reads AVAMD_EVAL_REPORT
-        # (default "0"); off: none of that code runs
-        self.eval_report = os.environ.get("AVAMD_EVAL_REPORT", "0") == "1" if eval_report is None else bool(eval_report)
-        self.last_report = None
-        # opt-in: minimum word error rate training (mwer.mwer_loss: n-best beam search, error counts and the n-best CTC loss of
-        # csrc/ctc_loss.hip, all on the device).  With mwer_weight > 0 and gradients enabled forward_losses adds
-        # mwer_weight * (mwer1 + mwer2) / 2 to ``total``; evaluate()'s loss stays the CTC loss.  None reads AVAMD_MWER_WEIGHT (default "0"),
-        # AVAMD_MWER_NBEST (4) and AVAMD_MWER_BEAM (8); weight 0: none of that code runs
-        self.mwer_weight = float(os.environ.get("AVAMD_MWER_WEIGHT", "0")) if mwer_weight is None else float(mwer_weight)
-        self.mwer_nbest = int(os.environ.get("AVAMD_MWER_NBEST", "4")) if mwer_nbest is None else int(mwer_nbest)
-        self.mwer_beam = int(os.environ.get("AVAMD_MWER_BEAM", "8")) if mwer_beam is None else int(mwer_beam)
-        self.mwer_level = mwer_level
-        if not 0.0 <= self.mwer_weight < float("inf"):         # NaN fails both comparisons
-            raise ValueError(f"mwer_weight must be finite and >= 0, got {self.mwer_weight}")
-        if not 1 <= self.mwer_nbest <= self.mwer_beam <= 64:
-            raise ValueError(f"need 1 <= mwer_nbest <= mwer_beam <= 64, got mwer_nbest={self.mwer_nbest} mwer_beam={self.mwer_beam}")
-        if mwer_level not in ("word", "char", "token"):
-            raise ValueError(f"mwer_level must be 'word', 'char' or 'token', got {mwer_level!r}")
+        opt = options.resolve
+        self.native_ctc = opt("native_ctc", native_ctc)
+        self._resolve_decode(eval_beam_width, eval_lm, eval_lm_weight, eval_token_bonus, eval_bias, eval_bias_weight)
+        self.eval_report, self.last_report = opt("eval_report", eval_report), None
+        self.mwer_weight, self.mwer_nbest = opt("mwer_weight", mwer_weight), opt("mwer_nbest", mwer_nbest)
+        self.mwer_beam, self.mwer_level = opt("mwer_beam", mwer_beam), mwer_level
+        options.check_mwer(self.mwer_weight, self.mwer_nbest, self.mwer_beam, mwer_level)
         self._mwer_table = None                                # the tokenizer's PieceTable, built once when the term first runs
-        # opt-in: data augmentation on the device (augment.Augment, csrc/augment.hip): in a training step forward_losses feeds the encoders
-        # shifted / mirrored / frame-frozen lip clips and the mixture with noise at a drawn SNR, written into buffers this trainer owns (the
-        # batch's tensors are never written).  augment: an Augment; None reads AVAMD_AUG_SHIFT / _FLIP / _TMASK / _TMASK_EVERY / _SNR / _SEED
-        # (augment.Augment.from_env: nothing set = off).  evaluate() and align() never augment.  Off: none of that code runs and no buffer
-        # exists.  Data parallel: each rank adds its rank to the seed, as the dropout generator does
+        # augmentation on the device (augment.Augment: None reads AVAMD_AUG_*, nothing set = off): in a training step forward_losses feeds the
+        # encoders augmented lip clips and mixture, written into buffers this trainer owns; evaluate() and align() never augment
         if augment is not None and not isinstance(augment, Augment):
             raise TypeError(f"augment must be an augment.Augment or None, got {type(augment).__name__}")
         self.augment = Augment.from_env() if augment is None else augment
@@ -161,35 +103,18 @@ class MultimodalTrainer:
         self.last_aug_sigma = None                             # noise level per item of the last augmented step, device float32 [B]
         self.parameters = (list(self.visual_encoder.parameters()) + list(self.audio_encoder.parameters())
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
-        # opt-in: global-norm gradient clipping and a linear warmup / decay of the learning rate inside the fused Adam step (optim.AvAdam,
-        # av_adam_multi_ex: norm, clip coefficient and schedule step live on the device, the step still holds no synchronising call).
-        # max_grad_norm: torch.nn.utils.clip_grad_norm_'s law; None reads AVAMD_CLIP_NORM (default "0" = off).  warmup_steps / total_steps:
-        # optim.lr_multiplier, one multiplier for all four groups (with a warmup the first step runs at multiplier 0, as torch's LambdaLR
-        # does); None reads AVAMD_WARMUP_STEPS / AVAMD_TOTAL_STEPS (default "0").  All off: none of that code runs.  Data parallel: the norm
-        # is taken after the all-reduce, over grad * grad_scale, so every rank computes the same bits from the same bytes
-        max_grad_norm = float(os.environ.get("AVAMD_CLIP_NORM", "0")) if max_grad_norm is None else float(max_grad_norm)
-        warmup_steps = int(os.environ.get("AVAMD_WARMUP_STEPS", "0")) if warmup_steps is None else int(warmup_steps)
-        total_steps = int(os.environ.get("AVAMD_TOTAL_STEPS", "0")) if total_steps is None else int(total_steps)
-        # opt-in: an exponential moving average of the trainable weights kept inside the same fused step (optim.AvAdam(ema_decay=...),
-        # av_adam_multi_ema: skipped with an overflowing step on the device, moved for LayerDrop-ped layers too, no synchronising call).
-        # ema_decay: None reads AVAMD_EMA_DECAY (default "0" = off); ema_warmup: optim.ema_decay's warmup, None reads AVAMD_EMA_WARMUP
-        # ("0").  eval_ema: evaluate() and align() run with the averaged weights (optimizer.averaged(): swapped in and back in place;
-        # BatchNorm buffers are not averaged, torch.optim.swa_utils.AveragedModel's default); None reads AVAMD_EVAL_EMA ("0").  Off: none of
-        # that code runs.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated
-        ema_decay = float(os.environ.get("AVAMD_EMA_DECAY", "0")) if ema_decay is None else float(ema_decay)
-        ema_warmup = os.environ.get("AVAMD_EMA_WARMUP", "0") == "1" if ema_warmup is None else bool(ema_warmup)
-        self.eval_ema = os.environ.get("AVAMD_EVAL_EMA", "0") == "1" if eval_ema is None else bool(eval_ema)
-        if self.eval_ema and not ema_decay > 0:
-            raise ValueError("eval_ema needs ema_decay > 0: there is no averaged model to evaluate")
+        self.max_grad_norm, self.warmup_steps = opt("max_grad_norm", max_grad_norm), opt("warmup_steps", warmup_steps)
+        self.total_steps = opt("total_steps", total_steps)
+        self.ema_decay, self.ema_warmup = opt("ema_decay", ema_decay), opt("ema_warmup", ema_warmup)
+        self.eval_ema = opt("eval_ema", eval_ema)
+        options.check_ema(self.eval_ema, self.ema_decay)
         self.optimizer = AvAdam([
             {"params": list(self.visual_encoder.parameters()), "lr": learning_rate},
             {"params": list(self.audio_encoder.parameters()), "lr": 2e-5},
             {"params": list(self.fusion_module.parameters()), "lr": learning_rate},
             {"params": list(self.decoder1.parameters()), "lr": learning_rate},
-        ], max_grad_norm=max_grad_norm, warmup_steps=warmup_steps, total_steps=total_steps, ema_decay=ema_decay,
-            ema_warmup=ema_warmup)                                                          # ValueError on bad values
-        self.max_grad_norm, self.warmup_steps, self.total_steps = max_grad_norm, warmup_steps, total_steps
-        self.ema_decay, self.ema_warmup = ema_decay, ema_warmup
+        ], max_grad_norm=self.max_grad_norm, warmup_steps=self.warmup_steps, total_steps=self.total_steps, ema_decay=self.ema_decay,
+            ema_warmup=self.ema_warmup)                                                     # ValueError on bad values
         # model/trainer.py:40 (GradScaler); off by default: bf16 operands need no loss scaling.  On = the reference's overflow-skip /
         # growth / backoff law, evaluated on the device
         self.scaler = AvGradScaler(device=device, enabled=loss_scaling)
@@ -201,28 +126,49 @@ class MultimodalTrainer:
         self.fusion_module.grad_arena = self.decoder1.grad_arena = self._head_arena
         self.reducer = reducer
         if reducer is not None:
-            self.optimizer.grad_scale = 1.0 / reducer.world
-            if reducer.world > 1:
-                # the collective schedule must not depend on the rank: LayerDrop decisions come from a generator seeded identically
-                # everywhere (every rank draws once per layer and pass), dropout masks from one seeded per rank
-                import torch.distributed as dist
-                m = self.audio_encoder.model
-                m.layerdrop_generator = torch.Generator().manual_seed(0x5EED1A7E)
-                m.dropout_generator = torch.Generator().manual_seed(0xD120 + 7919 * dist.get_rank(reducer.group))
-                if self.augment is not None:
-                    self.augment.rank_offset = dist.get_rank(reducer.group)
-            self.audio_encoder.model.grad_ready = reducer.reduce_async
-            self.audio_encoder.model.grad_flat_ready = reducer.reduce_flat
-            self.audio_encoder.model.grad_wait = reducer.wait
-            self._head_params = [p for m in (self.decoder1, self.fusion_module) for n, p in m.named_parameters()
-                                 if not n.startswith("cross_attn_visual.")]
-            # decoder + fusion gradients are complete when the wav2vec2 backward starts (their AccumulateGrad nodes run with top
-            # priority right after the fusion backward): start their all-reduce there, under the whole audio backward
-            self._head_done = False
-            if pair_batched:                                   # one fusion / decoder call per step: no later accumulation into these grads
-                self.audio_encoder.model.grad_pre = self._reduce_head_early
+            self._attach_reducer(reducer)
 
-    # ------------------------------------------------------------------------------------------------------------
+    def _resolve_decode(self, beam, lm, lm_weight, token_bonus, bias, bias_weight):
+        """evaluate()'s decoder settings; a path is loaded here.  The language model and the phrases are used only by the beam search."""
+        opt, tok = options.resolve, self.tokenizer
+        self.eval_beam_width = opt("eval_beam_width", beam)
+        if self.eval_beam_width < 0:
+            raise ValueError(f"eval_beam_width must be >= 0, got {self.eval_beam_width}")
+        lm = opt("eval_lm", lm)
+        if isinstance(lm, (str, os.PathLike)):
+            lm = NGramLM.from_arpa(os.fspath(lm), tok.token_to_id, vocab_size=tok.vocab_size, blank=tok.blank_id)
+        self.eval_lm, self.eval_lm_weight = lm, opt("eval_lm_weight", lm_weight)
+        self.eval_token_bonus = opt("eval_token_bonus", token_bonus)
+        options.check_decode(self.eval_beam_width, "eval_lm", lm, "language model")
+        bias = opt("eval_bias", bias)
+        if isinstance(bias, (str, os.PathLike)):
+            bias = ContextBias.from_file(os.fspath(bias), tok)
+        self.eval_bias, self.eval_bias_weight = bias, opt("eval_bias_weight", bias_weight)
+        options.check_decode(self.eval_beam_width, "eval_bias", bias, "phrase biasing")
+
+    def _attach_reducer(self, reducer):
+        """Data parallelism: gradient buckets go to ``reducer`` as the backward produces them, the fused Adam averages over the ranks."""
+        self.optimizer.grad_scale = 1.0 / reducer.world
+        if reducer.world > 1:
+            # the collective schedule must not depend on the rank: LayerDrop decisions come from a generator seeded identically
+            # everywhere (every rank draws once per layer and pass), dropout masks and augmentation plans from ones seeded per rank
+            import torch.distributed as dist
+            m = self.audio_encoder.model
+            m.layerdrop_generator = torch.Generator().manual_seed(0x5EED1A7E)
+            m.dropout_generator = torch.Generator().manual_seed(0xD120 + 7919 * dist.get_rank(reducer.group))
+            if self.augment is not None:
+                self.augment.rank_offset = dist.get_rank(reducer.group)
+        self.audio_encoder.model.grad_ready = reducer.reduce_async
+        self.audio_encoder.model.grad_flat_ready = reducer.reduce_flat
+        self.audio_encoder.model.grad_wait = reducer.wait
+        self._head_params = [p for m in (self.decoder1, self.fusion_module) for n, p in m.named_parameters()
+                             if not n.startswith("cross_attn_visual.")]
+        # decoder + fusion gradients are complete when the wav2vec2 backward starts (their AccumulateGrad nodes run with top
+        # priority right after the fusion backward): start their all-reduce there, under the whole audio backward
+        self._head_done = False
+        if self.pair_batched:                              # one fusion / decoder call per step: no later accumulation into these grads
+            self.audio_encoder.model.grad_pre = self._reduce_head_early
+
     def _to_dev(self, batch):
         dev = self.device
         nb = lambda t: t.to(dev, non_blocking=True)
@@ -238,92 +184,76 @@ class MultimodalTrainer:
         L.check(L.lib().av_mask_downsample(ops.ptr(mask.contiguous()), ops.ptr(out), B, Tin, T_enc, ops.stream()), "av_mask_downsample")
         return out
 
-    @staticmethod
-    def _mask_ds_host(mask_cpu: torch.Tensor, T_enc: int) -> torch.Tensor:
-        """Host restatement of av_mask_downsample (nearest index floor(i * Tin / T_enc), fp32 as on the device)."""
-        mask_cpu = mask_cpu.cpu()
-        Tin = mask_cpu.shape[1]
-        scale = torch.tensor(Tin / T_enc, dtype=torch.float32)
-        idx = torch.floor(torch.arange(T_enc, dtype=torch.float32) * scale).long().clamp_(max=Tin - 1)
-        return mask_cpu[:, idx]
-
-    @staticmethod
-    def _class_counts(mask_cpu: torch.Tensor, T_enc: int):
-        """(#1, #2, #0) of the down-sampled mask, computed on the host copy of the batch (no device sync when the
-        batch arrives from a DataLoader; a device-resident batch should carry precomputed ``_counts1/_counts2``)."""
-        c = torch.bincount(MultimodalTrainer._mask_ds_host(mask_cpu, T_enc).reshape(-1).clamp(0, 3), minlength=4).tolist()
-        return (c[1], c[2], c[0])
-
-    @staticmethod
-    def _fusion_lengths_host(mask_cpu: torch.Tensor, T_enc: int, Tv: int) -> torch.Tensor:
-        """Host restatement of the ``input_lengths`` CrossAttentionFusion returns for ONE call (model/fusion_module.py:41-59 of the
-        reference; av_fusion_gather_lerp_fwd here): n_b speech frames (mask 1/2) are kept per item and padded to the call's
-        maximum Tm, the mask is resampled to Tv frames with nearest index floor(i * Tm / Tv), and the length is the number
-        of resampled positions that fall on a kept frame."""
-        import numpy as np
-        m = MultimodalTrainer._mask_ds_host(mask_cpu, T_enc)
-        n = ((m == 1) | (m == 2)).sum(1).numpy().astype(np.int64)
-        Tm = int(n.max()) if n.size else 0
-        i = np.arange(Tv, dtype=np.float32)
-        if Tm == Tv:
-            j = np.arange(Tv, dtype=np.int64)
-        else:
-            j = np.floor(i * (np.float32(Tm) / np.float32(Tv))).astype(np.int64)
-            j = np.minimum(j, max(Tm - 1, 0))
-        return torch.from_numpy((j[None, :] < n[:, None]).sum(1).astype(np.int64))
+    # host restatements of what the step would otherwise read back from the device (model/host_meta.py)
+    _mask_ds_host = staticmethod(host_meta.mask_ds_host)
+    _class_counts = staticmethod(host_meta.class_counts)
+    _fusion_lengths_host = staticmethod(host_meta.fusion_lengths_host)
 
     def host_metadata(self, cpu_batch: Dict[str, torch.Tensor], T_enc: int) -> Dict[str, object]:
-        """Everything the step would otherwise read back from the device, computed from the HOST copy of a collated batch:
-        contrastive class counts and the CTC length vectors (nn.functional.ctc_loss wants its lengths on the host; handing
-        it device tensors costs a full device synchronisation per call).  Keys start with ``_``; merge into the batch."""
-        Tv = cpu_batch["lip1"].shape[1]
-        il = torch.cat([self._fusion_lengths_host(cpu_batch["mask1"], T_enc, Tv), self._fusion_lengths_host(cpu_batch["mask2"], T_enc, Tv)])
-        tl = torch.cat([cpu_batch["text1_lengths"].cpu().long(), cpu_batch["text2_lengths"].cpu().long()])
-        return {"_counts1": self._class_counts(cpu_batch["mask1"], T_enc), "_counts2": self._class_counts(cpu_batch["mask2"], T_enc),
-                "_ctc_input_lengths": il, "_ctc_target_lengths": tl,
-                "_same_padding": bool(torch.equal(cpu_batch["mask1"] != 3, cpu_batch["mask2"] != 3)),
-                "_audio_valid1": (cpu_batch["mask1"] != 3).sum(1).tolist(), "_audio_valid2": (cpu_batch["mask2"] != 3).sum(1).tolist()}
+        return host_meta.host_metadata(cpu_batch, T_enc)
 
     def forward_losses(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """model/trainer.py:66-119 for one batch; everything stays on the device.
-
+        """model/trainer.py:66-119 for one batch; everything stays on the device.  The stages below enqueue in the order they are called in.
         With ``native_ctc`` nothing in here synchronises, so the BiLSTM timeout words staged by a step are normally evaluated at the
         start of the NEXT call (or at the end of train_epoch / evaluate()): the RuntimeError of a timed-out persistent LSTM launch then
         names the previous step, not the one that is being enqueued."""
+        d = self._inputs(batch)
+        vf1, vf2, join = self._lips(d)
+        a1, mid1, a2, mid2 = self._audio(d, batch)
+        T_enc = a1.shape[1]
+        m1, m2 = self._mask_ds(d["mask1"], T_enc), self._mask_ds(d["mask2"], T_enc)
+        c1, c2 = self._contrastive(batch, mid1, mid2, m1, m2, T_enc)
+        join()
+        f1, f2, il1, il2, lp1, lp2, lp12, il12 = self._heads(vf1, vf2, a1, a2, m1, m2)
+        if lp12 is not None:
+            total, l1, l2, tg, tl = self._ctc_stacked(d, batch, lp12, il12, c1, c2)
+        else:
+            total, tg, tl = None, None, None
+            l1, l2 = self._ctc_per_speaker(d, lp1, lp2, il1, il2)
+        if total is None:
+            total = (l1 + l2) / 2 + self.lambda_ * (c1 + c2) / 2
+        out = {}
+        if self.mwer_weight > 0 and torch.is_grad_enabled():
+            mw1, mw2 = self._mwer_term(d, lp1, lp2, il1, il2, lp12, il12, tg, tl)
+            total = total + self.mwer_weight * (mw1 + mw2) / 2
+            out.update(mwer1=mw1, mwer2=mw2)
+        out.update(visual_feat1=vf1, visual_feat2=vf2, audio_last=a1, audio_mid=mid1, fused1=f1, fused2=f2, input_lengths1=il1,
+                   input_lengths2=il2, log_probs1=lp1, log_probs2=lp2, loss1=l1, loss2=l2, contrast1=c1, contrast2=c2, total=total)
+        return out
+
+    def _inputs(self, batch):
+        """Main stream: the batch's device copy and, in a training step with ``augment``, its augmented lips and mixture.  Before that the
+        timeout words the previous step staged are looked at (``native_ctc``: their event has completed unless the host runs far ahead)."""
         if self.native_ctc:
-            self.fusion_module.finish_flag_check(wait=True)        # staged one step ago: its event has completed unless the host runs far ahead
+            self.fusion_module.finish_flag_check(wait=True)
         d = self._to_dev(batch)
         if self.augment is not None and torch.is_grad_enabled() and self.decoder1.training and self.audio_encoder.training:
-            self._augment_inputs(d, batch)                         # on the main stream, before the lip streams fork
-        use_side = self.visual_side_stream and d["audio"].is_cuda
-        if use_side:
-            # the frozen visual encoder runs beside the wav2vec2 forward, one stream per speaker: its HBM-bound BatchNorm / pooling passes overlap
-            # the other streams' MFMA-bound kernels
-            dev_ = d["audio"].device
-            if self._vstream is None:
-                self._vstream = torch.cuda.Stream(device=dev_)
-                self._vstream2 = torch.cuda.Stream(device=dev_) if _VIS_STREAMS >= 2 else self._vstream
-            main = torch.cuda.current_stream(dev_)
-            two = self._vstream2 is not self._vstream
-            evs = []
-            from ..precision import compute_dtype
-            self.visual_encoder.warm_caches(compute_dtype())       # weight re-layouts are built on main, before the lip streams fork
-            self._vstream.wait_stream(main)
-            with torch.cuda.stream(self._vstream):
-                if two:
-                    self.visual_encoder._bn_sync, self.visual_encoder._bn_idx = ("lead", evs), 0
-                vf1 = self.visual_encoder(d["lip1"])
-            if two:
-                self._vstream2.wait_stream(main)
-                self.visual_encoder._bn_sync, self.visual_encoder._bn_idx = ("follow", evs), 0
-            try:
-                with torch.cuda.stream(self._vstream2):
-                    vf2 = self.visual_encoder(d["lip2"])
-            finally:
-                self.visual_encoder._bn_sync = None
-        else:
-            vf1 = self.visual_encoder(d["lip1"])
-            vf2 = self.visual_encoder(d["lip2"])
+            self._augment_inputs(d, batch)                         # before the lip streams fork
+        return d
+
+    def _lips(self, d):
+        """The frozen visual encoder for both speakers -> (feat1, feat2, join).  With ``visual_side_stream`` it runs beside the wav2vec2 forward
+        on side streams forked from main, one per speaker (AVAMD_VISUAL_STREAMS=1: both on one): its HBM-bound BatchNorm / pooling passes overlap
+        the other streams' MFMA-bound kernels.  ``join()`` makes main wait for them; otherwise two calls on main and ``join`` does nothing."""
+        if not (self.visual_side_stream and d["audio"].is_cuda):
+            return self.visual_encoder(d["lip1"]), self.visual_encoder(d["lip2"]), lambda: None
+        dev = d["audio"].device
+        if self._vstream is None:
+            self._vstream = torch.cuda.Stream(device=dev)
+            self._vstream2 = torch.cuda.Stream(device=dev) if _VIS_STREAMS >= 2 else self._vstream
+        main = torch.cuda.current_stream(dev)
+        vf1, vf2 = self.visual_encoder.forward_pair(d["lip1"], d["lip2"], (self._vstream, self._vstream2))
+
+        def join():
+            main.wait_stream(self._vstream)
+            if self._vstream2 is not self._vstream:
+                main.wait_stream(self._vstream2)
+            vf1.record_stream(main); vf2.record_stream(main)
+        return vf1, vf2, join
+
+    def _audio(self, d, batch):
+        """Main stream: wav2vec2 -> (last1, mid1, last2, mid2).  One pass stands for both speakers unless a stochastic regulariser is active in
+        train mode (``audio_passes`` forces either); two passes are one forward_pair call over one conv feature-extractor run."""
         attn1 = d["mask1"] != 3
         passes = self.audio_passes
         if passes is None:      # auto: the duplicate pass only differs when a stochastic regulariser is active in train mode
@@ -345,98 +275,87 @@ class MultimodalTrainer:
             if v1 is None and not batch["mask1"].is_cuda:                        # batch straight from a DataLoader: the masks ARE on the host
                 v1, v2 = (batch["mask1"] != 3).sum(1).tolist(), (batch["mask2"] != 3).sum(1).tolist()
             if passes == 2:
-                a1, mid1, a2, mid2 = self.audio_encoder.forward_pair(d["audio"], attn1, d["mask2"] != 3, v1, v2)
-            else:
-                a1, mid1 = self.audio_encoder(d["audio"], attention_mask=attn1, valid_lengths=v1)
-                a2, mid2 = a1, mid1
+                return self.audio_encoder.forward_pair(d["audio"], attn1, d["mask2"] != 3, v1, v2)
+            a1, mid1 = self.audio_encoder(d["audio"], attention_mask=attn1, valid_lengths=v1)
+            return a1, mid1, a1, mid1
         finally:
             self.audio_encoder.model._feat_cache = None
-        T_enc, D = a1.shape[1], a1.shape[2]
-        m1 = self._mask_ds(d["mask1"], T_enc)
-        m2 = self._mask_ds(d["mask2"], T_enc)
-        out = {}
-        if self.lambda_ != 0:
-            if self.projection_layer is None:
-                self.projection_layer = nn.Linear(D, 128).to(self.device)          # model/trainer.py:105-106
-                if self.fixed_projection is not None:
-                    with torch.no_grad():
-                        self.projection_layer.weight.copy_(self.fixed_projection[0]); self.projection_layer.bias.copy_(self.fixed_projection[1])
-            k1 = batch.get("_counts1") or self._class_counts(batch["mask1"], T_enc)
-            k2 = batch.get("_counts2") or self._class_counts(batch["mask2"], T_enc)
-            c1 = contrastive_loss_with_mask(mid1, m1.reshape(-1), self.projection_layer, counts=k1)
-            c2 = contrastive_loss_with_mask(mid2, m2.reshape(-1), self.projection_layer, counts=k2)
-        else:
-            c1 = c2 = torch.zeros((), device=a1.device)
-        if use_side:
-            main.wait_stream(self._vstream)
-            if self._vstream2 is not self._vstream:
-                main.wait_stream(self._vstream2)
-            vf1.record_stream(main); vf2.record_stream(main)
+
+    def _contrastive(self, batch, mid1, mid2, m1, m2, T_enc):
+        """Main stream: the contrastive terms (c1, c2) of the mid-layer features; zeros at ``lambda_`` 0.  The projection layer is made on first use."""
+        if self.lambda_ == 0:
+            return (torch.zeros((), device=mid1.device),) * 2
+        if self.projection_layer is None:
+            self.projection_layer = nn.Linear(mid1.shape[2], 128).to(self.device)          # model/trainer.py:105-106
+            if self.fixed_projection is not None:
+                with torch.no_grad():
+                    self.projection_layer.weight.copy_(self.fixed_projection[0]); self.projection_layer.bias.copy_(self.fixed_projection[1])
+        k1 = batch.get("_counts1") or self._class_counts(batch["mask1"], T_enc)
+        k2 = batch.get("_counts2") or self._class_counts(batch["mask2"], T_enc)
+        return (contrastive_loss_with_mask(mid1, m1.reshape(-1), self.projection_layer, counts=k1),
+                contrastive_loss_with_mask(mid2, m2.reshape(-1), self.projection_layer, counts=k2))
+
+    def _heads(self, vf1, vf2, a1, a2, m1, m2):
+        """Main stream: fusion and decoder -> (fused1, fused2, lengths1, lengths2, log_probs1, log_probs2, log_probs12, lengths12).  One stacked
+        call (the last two are its results, else None) only if the lip clips were padded to the same length: the reference's collate pads lip1
+        and lip2 separately (dataset/collate_fn.py:8-13,27-31), so a real batch can differ - then one call per speaker, as the reference does
+        (found by tests/test_dataset_gpu.py::test_dataset_feeds_the_training_step).  Sets ``_pair_step`` for the head bucket's early reduce."""
         B = a1.shape[0]
-        # the two speakers go through fusion / decoder / CTC as one stacked call only if their lip clips were padded to the same length;
-        # the reference's collate pads lip1 and lip2 separately (dataset/collate_fn.py:8-13,27-31), so a real batch can differ - then one
-        # call per speaker, as the reference does (found by tests/test_dataset_gpu.py::test_dataset_feeds_the_training_step)
-        pair = self.pair_batched and vf1.shape[1] == vf2.shape[1]
-        self._pair_step = pair
+        pair = self._pair_step = self.pair_batched and vf1.shape[1] == vf2.shape[1]
         if pair:
             f12, il12 = self.fusion_module(torch.cat([vf1, vf2], 0), torch.cat([a1, a2], 0), mask=torch.cat([m1, m2], 0), groups=2)
             lp12 = self.decoder1(f12)
-            f1, f2, il1, il2, lp1, lp2 = f12[:B], f12[B:], il12[:B], il12[B:], lp12[:B], lp12[B:]
+            return f12[:B], f12[B:], il12[:B], il12[B:], lp12[:B], lp12[B:], lp12, il12
+        f1, il1 = self.fusion_module(vf1, a1, mask=m1)
+        f2, il2 = self.fusion_module(vf2, a2, mask=m2)
+        return f1, f2, il1, il2, self.decoder1(f1), self.decoder1(f2), None, None
+
+    def _ctc_stacked(self, d, batch, lp12, il12, c1, c2):
+        """Main stream: ONE CTC call over the 2B items -> (total or None, loss1, loss2, targets, target lengths); the 'mean' reduction of
+        nn.CTCLoss = mean_i(nll_i / clamp(target_len_i, 1)) is re-applied per speaker half, with the contrastive terms in one kernel
+        (_CombineFn) where that applies.  nn.functional.ctc_loss (PyTorch-ROCm, as north_star prescribes) synchronises unless the batch
+        carries host_metadata()'s lengths; ops.ctc_loss reads lengths and targets from device memory and nothing blocks (the staged timeout
+        words are then looked at only if their copy happens to be complete, otherwise by the next forward_losses / train_epoch / evaluate())."""
+        B = lp12.shape[0] // 2
+        t1, t2 = d["text1"], d["text2"]
+        Lm = max(t1.shape[1], t2.shape[1])
+        tg = torch.cat([F.pad(t1, (0, Lm - t1.shape[1])), F.pad(t2, (0, Lm - t2.shape[1]))], 0)
+        tl = torch.cat([d["text1_lengths"], d["text2_lengths"]], 0)
+        il_h, tl_h = batch.get("_ctc_input_lengths"), batch.get("_ctc_target_lengths")     # host copies: no device sync in ctc_loss
+        w_ctc = (0.5 / B) / tl.clamp_min(1).to(torch.float32)        # weights of the per-speaker means (before the CTC call: off the sync)
+        self.fusion_module.stage_flag_check()                  # BiLSTM timeout words -> pinned memory, visible after ctc_loss's own sync
+        if self.native_ctc:
+            nll = ops.ctc_loss(lp12, tg, il12, tl, blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True, batch_first=True)
         else:
-            f1, il1 = self.fusion_module(vf1, a1, mask=m1)
-            f2, il2 = self.fusion_module(vf2, a2, mask=m2)
-            lp1 = self.decoder1(f1)
-            lp2 = self.decoder1(f2)
-        if pair:
-            # one nn.functional.ctc_loss call (PyTorch-ROCm, as north_star prescribes) over the 2B items; 'mean' reduction
-            # of nn.CTCLoss = mean_i(nll_i / clamp(target_len_i, 1)) is re-applied per speaker half
-            t1, t2 = d["text1"], d["text2"]
-            Lm = max(t1.shape[1], t2.shape[1])
-            tg = torch.cat([F.pad(t1, (0, Lm - t1.shape[1])), F.pad(t2, (0, Lm - t2.shape[1]))], 0)
-            tl = torch.cat([d["text1_lengths"], d["text2_lengths"]], 0)
-            il_h, tl_h = batch.get("_ctc_input_lengths"), batch.get("_ctc_target_lengths")     # host copies: no device sync in ctc_loss
-            w_ctc = (0.5 / B) / tl.clamp_min(1).to(torch.float32)        # weights of the per-speaker means (before the CTC call: off the sync)
-            self.fusion_module.stage_flag_check()                  # BiLSTM timeout words -> pinned memory, visible after ctc_loss's own sync
-            if self.native_ctc:
-                # device CTC: lengths and targets are read from device memory, nothing blocks (the staged words are looked at below if
-                # their copy happens to be complete, otherwise by the next forward_losses / train_epoch / evaluate())
-                nll = ops.ctc_loss(lp12, tg, il12, tl, blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True, batch_first=True)
-            else:
-                nll = F.ctc_loss(lp12.transpose(0, 1), tg, il12 if il_h is None else il_h, tl if tl_h is None else tl_h,
-                                 blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True)
-            self.fusion_module.finish_flag_check()                 # raises if a persistent BiLSTM launch timed out (event query, no sync)
-            if nll.is_cuda and nll.dtype == torch.float32 and _FUSED_LOSS:
-                total, l1, l2 = _CombineFn.apply(nll, w_ctc, c1, c2, float(self.lambda_))    # one kernel forward, one backward
-            else:
-                per = nll / tl.clamp_min(1).to(nll.dtype)
-                l1, l2 = per[:B].mean(), per[B:].mean()
-                total = None
-        else:
-            total = None
-            if self.native_ctc:
-                kw = dict(blank=self.tokenizer.blank_id, reduction="mean", zero_infinity=True, batch_first=True)
-                self.fusion_module.stage_flag_check()
-                l1 = ops.ctc_loss(lp1, d["text1"], il1, d["text1_lengths"], **kw)
-                l2 = ops.ctc_loss(lp2, d["text2"], il2, d["text2_lengths"], **kw)
-                self.fusion_module.finish_flag_check()
-            else:
-                l1 = self.ctc_loss(lp1.transpose(0, 1), d["text1"], il1, d["text1_lengths"])
-                l2 = self.ctc_loss(lp2.transpose(0, 1), d["text2"], il2, d["text2_lengths"])
-        if total is None:
-            total = (l1 + l2) / 2 + self.lambda_ * (c1 + c2) / 2
-        if self.mwer_weight > 0 and torch.is_grad_enabled():
-            # the MWER term meets the CTC term at the log-probs through autograd, as the contrastive and CTC terms meet further down
-            if pair:
-                per = self._mwer(lp12, tg, tl, il12)
-                mw1, mw2 = per[:B].mean(), per[B:].mean()
-            else:
-                mw1 = self._mwer(lp1, d["text1"], d["text1_lengths"], il1).mean()
-                mw2 = self._mwer(lp2, d["text2"], d["text2_lengths"], il2).mean()
-            total = total + self.mwer_weight * (mw1 + mw2) / 2
-            out.update(mwer1=mw1, mwer2=mw2)
-        out.update(visual_feat1=vf1, visual_feat2=vf2, audio_last=a1, audio_mid=mid1, fused1=f1, fused2=f2, input_lengths1=il1,
-                   input_lengths2=il2, log_probs1=lp1, log_probs2=lp2, loss1=l1, loss2=l2, contrast1=c1, contrast2=c2, total=total)
-        return out
+            nll = F.ctc_loss(lp12.transpose(0, 1), tg, il12 if il_h is None else il_h, tl if tl_h is None else tl_h,
+                             blank=self.tokenizer.blank_id, reduction="none", zero_infinity=True)
+        self.fusion_module.finish_flag_check()                 # raises if a persistent BiLSTM launch timed out (event query, no sync)
+        if nll.is_cuda and nll.dtype == torch.float32 and _FUSED_LOSS:
+            return (*_CombineFn.apply(nll, w_ctc, c1, c2, float(self.lambda_)), tg, tl)      # one kernel forward, one backward
+        per = nll / tl.clamp_min(1).to(nll.dtype)
+        return None, per[:B].mean(), per[B:].mean(), tg, tl
+
+    def _ctc_per_speaker(self, d, lp1, lp2, il1, il2):
+        """Main stream: one mean-reduced CTC call per speaker -> (loss1, loss2), as the reference does; nn.CTCLoss synchronises in each."""
+        if not self.native_ctc:
+            return (self.ctc_loss(lp1.transpose(0, 1), d["text1"], il1, d["text1_lengths"]),
+                    self.ctc_loss(lp2.transpose(0, 1), d["text2"], il2, d["text2_lengths"]))
+        kw = dict(blank=self.tokenizer.blank_id, reduction="mean", zero_infinity=True, batch_first=True)
+        self.fusion_module.stage_flag_check()
+        l1 = ops.ctc_loss(lp1, d["text1"], il1, d["text1_lengths"], **kw)
+        l2 = ops.ctc_loss(lp2, d["text2"], il2, d["text2_lengths"], **kw)
+        self.fusion_module.finish_flag_check()
+        return l1, l2
+
+    def _mwer_term(self, d, lp1, lp2, il1, il2, lp12, il12, tg, tl):
+        """Main stream: the mean MWER risk per speaker (mwer1, mwer2), from one ``_mwer`` call on the stacked log-probs or one per speaker.  The
+        term meets the CTC term at the log-probs through autograd, as the contrastive and CTC terms meet further down."""
+        if lp12 is not None:
+            B = lp12.shape[0] // 2
+            per = self._mwer(lp12, tg, tl, il12)
+            return per[:B].mean(), per[B:].mean()
+        return (self._mwer(lp1, d["text1"], d["text1_lengths"], il1).mean(),
+                self._mwer(lp2, d["text2"], d["text2_lengths"], il2).mean())
 
     def _aug_buffer(self, name: str, like: torch.Tensor) -> torch.Tensor:
         buf = self._aug_buf.get(name)
@@ -454,18 +373,13 @@ class MultimodalTrainer:
                 key = f"lip{spk}"
                 d[key] = aug.lips(d[key], batch.get(key + "_lengths"), aug.step, spk, out=self._aug_buffer(key, d[key]))
         if aug.noise_on:
-            B = d["audio"].shape[0]
-            sg = self._aug_buf.get("sigma")
-            if sg is None or sg.shape[0] != B or sg.device != d["audio"].device:
-                sg = self._aug_buf["sigma"] = torch.empty((B,), dtype=torch.float32, device=d["audio"].device)
-            d["audio"], self.last_aug_sigma = aug.noise(d["audio"], (d["mask1"] != 3).sum(1), aug.step,
-                                                        out=self._aug_buffer("audio", d["audio"]), sigma=sg)
+            d["audio"], self.last_aug_sigma = aug.noise(d["audio"], (d["mask1"] != 3).sum(1), aug.step, out=self._aug_buffer("audio", d["audio"]),
+                                                        sigma=self._aug_buffer("sigma", d["audio"][:, 0]))
 
     def _mwer(self, lp, refs, ref_lengths, input_lengths):
         """Per-utterance MWER risk [B] of one decoder call (mwer.mwer_loss, reduction "none"); float32 log-probs as the CTC loss reads them."""
         from ..mwer import mwer_loss
         if self.mwer_level != "token" and self._mwer_table is None:
-            from ..error_rate import PieceTable
             self._mwer_table = PieceTable.from_tokenizer(self.tokenizer)
         return mwer_loss(lp.float(), refs, ref_lengths, input_lengths, self.tokenizer.blank_id, nbest=self.mwer_nbest,
                          beam_width=self.mwer_beam, table=self._mwer_table, level=self.mwer_level, reduction="none")
@@ -556,48 +470,50 @@ class MultimodalTrainer:
             prev = idx
         return result
 
-    def evaluate(self, dataloader):
-        """(loss, WER) over the loader.  With ``eval_ema`` the loop runs on the averaged weights and the trained ones are back afterwards."""
-        if self.eval_ema:
-            with self.optimizer.averaged():
-                return self._evaluate(dataloader)
-        return self._evaluate(dataloader)
+    @contextlib.contextmanager
+    def _inference(self):
+        """What evaluate() and align() share: no autograd; with ``eval_ema`` the averaged weights inside the block and the trained ones after
+        it; no contrastive term (so no projection layer is created); with ``native_ctc`` every pending timeout word is looked at on the way out."""
+        with self.optimizer.averaged() if self.eval_ema else contextlib.nullcontext(), torch.no_grad():
+            lam, self.lambda_ = self.lambda_, 0.0
+            try:
+                yield
+                if self.native_ctc:
+                    self.fusion_module.drain_flag_check()
+            finally:
+                self.lambda_ = lam
 
-    @torch.no_grad()
-    def _evaluate(self, dataloader):
-        self.visual_encoder.eval(); self.audio_encoder.eval(); self.fusion_module.eval(); self.decoder1.eval()
+    def _decode(self, lp):
+        """Token ids per utterance: greedy (== the reference's simple_beam_search best beam) at ``eval_beam_width`` 0, otherwise the
+        prefix beam search, with shallow fusion and / or phrase biasing where set (it rejects their weights without ``lm=`` / ``bias=``)."""
+        if self.eval_beam_width == 0:
+            return greedy_batch(lp, self.tokenizer.blank_id)
+        kw = {}
+        if self.eval_lm is not None:
+            kw.update(lm=self.eval_lm, lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
+        if self.eval_bias is not None:
+            kw.update(bias=self.eval_bias, bias_weight=self.eval_bias_weight)
+        return prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, **kw)
+
+    def evaluate(self, dataloader):
+        """(loss, WER) over the loader, decoded by ``_decode``; the modules are left in eval mode."""
         refs1, hyps1, refs2, hyps2 = [], [], [], []
         total_loss = 0.0
-        lam, self.lambda_ = self.lambda_, 0.0
         self.last_report = None
-        report = self._report_begin() if self.eval_report else None
-        try:
+        with self._inference():
+            self.visual_encoder.eval(); self.audio_encoder.eval(); self.fusion_module.eval(); self.decoder1.eval()
+            report = self._report_begin() if self.eval_report else None
             for batch in dataloader:
                 out = self.forward_losses(batch)
                 total_loss += (out["loss1"].item() + out["loss2"].item()) / 2
                 for spk, lp, refs, hyps in (("1", out["log_probs1"], refs1, hyps1), ("2", out["log_probs2"], refs2, hyps2)):
-                    if self.eval_beam_width > 0 and self.eval_bias is not None:
-                        fusion = {} if self.eval_lm is None else dict(lm=self.eval_lm, lm_weight=self.eval_lm_weight,
-                                                                      token_bonus=self.eval_token_bonus)
-                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, bias=self.eval_bias,
-                                                 bias_weight=self.eval_bias_weight, **fusion)
-                    elif self.eval_beam_width > 0 and self.eval_lm is not None:
-                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id, lm=self.eval_lm,
-                                                 lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
-                    elif self.eval_beam_width > 0:
-                        ids = prefix_beam_search(lp, self.eval_beam_width, self.tokenizer.blank_id)
-                    else:
-                        ids = greedy_batch(lp, self.tokenizer.blank_id)   # == simple_beam_search best beam (SURVEY §0.3)
+                    ids = self._decode(lp)
                     txt, tl = batch["text" + spk], batch["text" + spk + "_lengths"]
                     for i, seq in enumerate(ids):
                         hyps.append(fast_decode(seq, self.tokenizer))
                         refs.append(self.tokenizer.decode(txt[i][: int(tl[i])].tolist()))
                     if report is not None:
                         self._report_add(report, spk, txt, tl, ids)
-            if self.native_ctc:
-                self.fusion_module.drain_flag_check()
-        finally:
-            self.lambda_ = lam
         if report is not None:
             wer1, wer2 = self._report_finish(report)
         else:
@@ -610,13 +526,11 @@ class MultimodalTrainer:
 
     # evaluate()'s opt-in report: error counts of both speakers on the device, one accumulator, one transfer after the loop
     def _report_begin(self):
-        from ..error_rate import PieceTable
         if torch.device(self.device).type != "cuda":
             raise RuntimeError("MultimodalTrainer.evaluate: eval_report counts errors on the GPU; there is no CPU fallback")
         return {"table": PieceTable.from_tokenizer(self.tokenizer), "acc": torch.zeros((2, 3, 4), dtype=torch.int64, device=self.device)}
 
     def _report_add(self, report, spk, txt, tl, ids):
-        from ..error_rate import error_counts
         # references as evaluate() decodes them (nothing skipped), hypotheses as fast_decode does (the blank skipped)
         counts = error_counts(txt.to(self.device, non_blocking=True), ids, ref_lengths=tl, table=report["table"], ref_skip=-1,
                               hyp_skip=self.tokenizer.blank_id)
@@ -624,47 +538,36 @@ class MultimodalTrainer:
         report["acc"][int(spk) - 1] += (best * (best[:, :, 3:4] >= 0)).sum(0)          # a level of -1 (a text beyond the limit) adds nothing
 
     def _report_finish(self, report):
-        from ..error_rate import rates
         acc = report["acc"].cpu()
         self.last_report = {"speaker1": rates(acc[0]), "speaker2": rates(acc[1])}
         return self.last_report["speaker1"]["word"]["rate"], self.last_report["speaker2"]["word"]["rate"]
 
-    def align(self, batch, frame_rate: float = 25.0):
-        """``_align`` - on the averaged weights with ``eval_ema``."""
-        if self.eval_ema:
-            with self.optimizer.averaged():
-                return self._align(batch, frame_rate)
-        return self._align(batch, frame_rate)
-
     @torch.no_grad()
-    def _align(self, batch, frame_rate: float = 25.0):
+    def align(self, batch, frame_rate: float = 25.0):
         """Word times of both speakers' transcripts in one batch: CTC forced alignment (align.forced_align, csrc/ctc_align.hip) of
         ``text*`` against the log-probs of ONE forward_losses call in eval mode.  Returns (segments1, segments2): per utterance the
         ``align.word_segments`` list ([] for a transcript that cannot be aligned).  The CTC head runs at the lip-frame rate, so
         ``frame_rate`` is the video's.  One device-to-host transfer per speaker; every module's train / eval mode is restored."""
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("MultimodalTrainer.align: the model runs on the GPU; there is no CPU fallback")
-        mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
-        modes = [(sm, sm.training) for m in mods for sm in m.modules()]      # per sub-module: a frozen part may sit in eval mode
-        for m in mods:
-            m.eval()
-        lam, self.lambda_ = self.lambda_, 0.0              # as evaluate(): no contrastive term (and no projection layer is created)
-        try:
-            out = self.forward_losses(batch)
-            if self.native_ctc:
-                self.fusion_module.drain_flag_check()
-            res = []
-            for spk in ("1", "2"):
-                txt, tl = batch["text" + spk], batch["text" + spk + "_lengths"]
-                al = forced_align(out["log_probs" + spk], txt, out["input_lengths" + spk], tl, blank=self.tokenizer.blank_id)
-                # spans and the token scores' bits in one int32 block [B][Lmax][3]: a single transfer
-                packed = torch.cat([al.spans, al.token_scores.view(torch.int32)[..., None]], dim=2).cpu()
-                spans, tok = packed[..., :2], packed[..., 2].contiguous().view(torch.float32)
-                txt_h, tl_h = txt.cpu(), tl.cpu().tolist()
-                res.append([word_segments(self.tokenizer, txt_h[i, :max(0, int(tl_h[i]))], spans[i], tok[i], frame_rate)
-                            for i in range(txt_h.shape[0])])
-        finally:
-            self.lambda_ = lam
-            for sm, was in modes:
-                sm.training = was
+        with self._inference():
+            if torch.device(self.device).type != "cuda":
+                raise RuntimeError("MultimodalTrainer.align: the model runs on the GPU; there is no CPU fallback")
+            mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+            modes = [(sm, sm.training) for m in mods for sm in m.modules()]      # per sub-module: a frozen part may sit in eval mode
+            for m in mods:
+                m.eval()
+            try:
+                out = self.forward_losses(batch)
+            finally:
+                for sm, was in modes:
+                    sm.training = was
+        res = []
+        for spk in ("1", "2"):
+            txt, tl = batch["text" + spk], batch["text" + spk + "_lengths"]
+            al = forced_align(out["log_probs" + spk], txt, out["input_lengths" + spk], tl, blank=self.tokenizer.blank_id)
+            # spans and the token scores' bits in one int32 block [B][Lmax][3]: a single transfer
+            packed = torch.cat([al.spans, al.token_scores.view(torch.int32)[..., None]], dim=2).cpu()
+            spans, tok = packed[..., :2], packed[..., 2].contiguous().view(torch.float32)
+            txt_h, tl_h = txt.cpu(), tl.cpu().tolist()
+            res.append([word_segments(self.tokenizer, txt_h[i, :max(0, int(tl_h[i]))], spans[i], tok[i], frame_rate)
+                        for i in range(txt_h.shape[0])])
         return tuple(res)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 import align_ref as R
 
 NAMES = ("av_ctc_align_workspace_bytes", "av_ctc_align")
@@ -202,14 +203,6 @@ def test_word_segments_on_hand_made_spans():
     assert A.word_segments(tok, ids, [[-1, -1]] * 8, [0.0] * 8) == []            # infeasible utterance
     assert A.word_segments(tok, [], [[-1, -1]] * 8, [0.0] * 8) == []             # empty transcript
     assert A.word_segments(tok, [sp, sp], [[0, 1], [1, 2]], [-0.1, -0.1]) == []  # nothing but spaces
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def test_trainer_align_has_no_cpu_fallback():

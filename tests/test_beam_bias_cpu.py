@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 import beam_ref as R
 import bias_ref as BR
 import lm_ref as LR
@@ -342,14 +343,6 @@ def test_abi_argument_errors_in_both_libraries():
             assert lib.av_context_bias_count(*a) != 0 and word in lib.av_last_error(), (where, lib.av_last_error())
         a = list(good); a[3] = 0
         assert lib.av_context_bias_count(*a) == 0                             # B = 0: nothing to do
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def test_trainer_takes_phrases_only_when_asked(monkeypatch, tmp_path):

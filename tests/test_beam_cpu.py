@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 import beam_ref as R
 
 
@@ -158,14 +159,6 @@ def test_abi_argument_errors_in_both_libraries():
         assert lib.av_ctc_beam_search(P, T * V, V, None, P, P, P, P, n, B, T, 1, 0, 5, 1, None) != 0
         assert lib.av_ctc_beam_search(P, T * V, V - 1, None, P, P, P, P, n, B, T, V, 0, 5, 1, None) != 0
         assert b"strides" in lib.av_last_error()
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def test_trainer_decodes_greedily_unless_asked(monkeypatch):

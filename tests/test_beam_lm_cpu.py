@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 import beam_ref as R
 import lm_ref as LR
 
@@ -280,14 +281,6 @@ def test_workspace_sizes_are_the_closed_forms_in_both_libraries():
                         got = ctypes.c_longlong(-1)
                         assert lib.av_ctc_beam_lm_workspace_bytes(B, T, 50, W, tokens, ctypes.byref(got)) == 0
                         assert got.value == 8 * B * T * (wf + 1) + 8 * B * T * max(W, wf), (B, T, W, tokens, got.value)
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def test_trainer_uses_a_language_model_only_when_asked(monkeypatch, tmp_path):

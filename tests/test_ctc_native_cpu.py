@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 
 NAMES = ("av_ctc_loss_fwd", "av_ctc_loss_bwd")
 
@@ -62,14 +63,6 @@ def test_ops_ctc_loss_has_no_cpu_fallback_and_rejects_1d_targets():
         ops.ctc_loss(lp, tg, il, tl)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         pkg("model.decoder").CTCDecoder(16, 8, 0, native_ctc=True)(torch.zeros(2, 5, 16), tg, il, tl)
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def test_native_ctc_is_off_by_default_and_follows_the_environment(monkeypatch):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 
 
 def _hf_lambda(warmup, total):
@@ -35,14 +36,6 @@ def test_lr_multiplier_is_lambdalr_with_the_hf_lambda(warmup, total):
         assert got == [0, 1 / 3, 2 / 3, 1, .75, .5, .25, 0, 0, 0]
     if (warmup, total) == (0, 0):
         assert got == [1.0] * 10
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def _opts(t):

@@ -5,6 +5,7 @@ import ctypes
 import pytest
 
 from conftest import pkg
+from trainer_util import cpu_trainer as _trainer
 
 
 @pytest.mark.parametrize("warmup", [False, True])
@@ -33,14 +34,6 @@ def test_check_ema_rejects_bad_decays():
             optim.check_ema(bad, False)
         with pytest.raises(ValueError):
             optim.AvAdam([__import__("torch").zeros(1, requires_grad=True)], ema_decay=bad)
-
-
-def _trainer(**kw):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    cfg = dict(init.W2V2_TINY)
-    return tr.MultimodalTrainer(enc.VisualEncoder(), enc.AudioEncoder(cfg, freeze=True), fm.CrossAttentionFusion(512, cfg["hidden_size"], 512),
-                                dm.CTCDecoder(1024, 800, 3), tok.SyntheticTokenizer(800), device="cpu", **kw)
 
 
 def _opts(t):

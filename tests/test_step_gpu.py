@@ -7,26 +7,10 @@ import pytest
 import torch
 
 from conftest import pkg
+from trainer_util import gpu_trainer as build        # the other GPU files import it from here
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def build(cfg, precision):
-    init = pkg("utils.init"); enc = pkg("model.encoder"); fm = pkg("model.fusion_module"); dm = pkg("model.decoder")
-    tr = pkg("model.trainer"); tok = pkg("utils.tokenizer")
-    pkg("precision").set_precision(precision)
-    ve = enc.VisualEncoder(); ve.load_state_dict(init.visual_state_dict())
-    for p in ve.parameters():
-        p.requires_grad = False                                        # main.py:100-103
-    ae = enc.AudioEncoder(dict(cfg), freeze=True); ae.load_state_dict(init.w2v2_state_dict(cfg))
-    for n, p in ae.model.named_parameters():                           # main.py:26-31
-        p.requires_grad = any(f"encoder.layers.{i}." in n for i in range(6, 10))
-    fu = fm.CrossAttentionFusion(512, cfg["hidden_size"], 512); fu.load_state_dict(init.fusion_state_dict(512, cfg["hidden_size"], 512))
-    de = dm.CTCDecoder(1024, 800, 3); de.load_state_dict(init.decoder_state_dict(1024, 800))
-    t = tr.MultimodalTrainer(ve, ae, fu, de, tok.SyntheticTokenizer(800), learning_rate=1e-4, device="cuda", lambda_=0.1)
-    t.fixed_projection = init.projection_params(cfg["hidden_size"])
-    return t
 
 
 def maxdiff(a, b):
