@@ -491,7 +491,7 @@ int av_adam_multi(const void* ptrs, const long long* sizes, const float* hyper, 
                   int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
                   float* scaler_state, float growth, float backoff, int growth_interval, void* stream);
 /* av_adam_multi with global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, both decided on the device
- * (csrc/loss_misc.hip; optim.AvAdam).  The arguments of av_adam_multi, and:
+ * (csrc/optim.hip; optim.AvAdam).  The arguments of av_adam_multi, and:
  * max_norm > 0: clip.  One more pass reads the gradients (sum of squares per chunk in double, no atomics: the same bits on every run),
  *   one workgroup adds the chunk sums in a fixed order, and the Adam kernel multiplies grad * grad_scale (/ scale) by
  *   min(1, max_norm / (norm + 1e-6)), the law of torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False (a NaN norm gives a NaN
@@ -510,7 +510,7 @@ int av_adam_multi_ex(const void* ptrs, const long long* sizes, const float* hype
                      float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
                      int total_steps, void* workspace, long long workspace_bytes, float* clip_state, void* stream);
 /* av_adam_multi_ex that also keeps an exponential moving average (EMA) of the weights, updated inside the same Adam launch while the new
- * parameter is still in a register (csrc/loss_misc.hip; optim.AvAdam(ema_decay=...)).  The arguments of av_adam_multi_ex, and:
+ * parameter is still in a register (csrc/optim.hip; optim.AvAdam(ema_decay=...)).  The arguments of av_adam_multi_ex, and:
  * ema_ptrs: [n_tensors] device pointers, the fp32 average of tensor t of the launch (a table of its own: ptrs stays [n_tensors][5]).
  * ema_only_ptrs [n_only][2] device pointers {param, ema}, ema_only_sizes [n_only], ema_only_chunk_tensor / ema_only_chunk_start
  *   [n_ema_only_chunks] (chunks of chunk_elems, as above): tensors that have an average but no gradient in this step (LayerDrop); a light

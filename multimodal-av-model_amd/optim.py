@@ -9,11 +9,18 @@ from __future__ import annotations
 
 import contextlib
 
+import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops
 from .utils import shadow
+
+# slots of the device state blocks, as csrc/optim.hip names them: loss scaling (five floats), clipping / schedule (three floats and an int32
+# step counter), EMA (a float and an int32 update counter)
+GS_SCALE, GS_INV, GS_INF, GS_TRACK, GS_STEP = range(5)
+CS_NORM, CS_COEF, CS_LRM, CS_K = range(4)
+ES_DECAY, ES_K = range(2)
 
 
 class AvGradScaler:
@@ -32,7 +39,7 @@ class AvGradScaler:
         self.state = torch.tensor([init_scale, 1.0 / init_scale, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
 
     def scale(self, loss: torch.Tensor) -> torch.Tensor:
-        return loss * self.state[0] if self.enabled else loss
+        return loss * self.state[GS_SCALE] if self.enabled else loss
 
     def step(self, optimizer: "AvAdam"):
         return optimizer.step(scaler=self if self.enabled else None)
@@ -41,21 +48,21 @@ class AvGradScaler:
         return None
 
     def get_scale(self) -> float:        # host synchronisation (diagnostics / checkpoints only)
-        return float(self.state[0])
+        return float(self.state[GS_SCALE])
 
     def steps_taken(self) -> int:
-        return int(self.state[4])
+        return int(self.state[GS_STEP])
 
     def state_dict(self):
         st = self.state.tolist()
-        return {"scale": st[0], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
-                "growth_interval": self.growth_interval, "_growth_tracker": int(st[3]), "_steps_taken": int(st[4])}
+        return {"scale": st[GS_SCALE], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": int(st[GS_TRACK]), "_steps_taken": int(st[GS_STEP])}
 
     def load_state_dict(self, sd):
         self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
         self.growth_interval = int(sd["growth_interval"])
-        self.state[0] = float(sd["scale"]); self.state[1] = 1.0 / float(sd["scale"]); self.state[3] = float(sd["_growth_tracker"])
-        self.state[4] = float(sd.get("_steps_taken", 0))
+        self.state[GS_SCALE] = float(sd["scale"]); self.state[GS_INV] = 1.0 / float(sd["scale"]); self.state[GS_TRACK] = float(sd["_growth_tracker"])
+        self.state[GS_STEP] = float(sd.get("_steps_taken", 0))
 
 
 def lr_multiplier(k: int, warmup_steps: int = 0, total_steps: int = 0) -> float:
@@ -102,13 +109,69 @@ def check_ema(decay, warmup=False):
     return decay, warmup
 
 
+def _chunk_table(numels, chunk):
+    """(chunk_tensor, chunk_start) of a multi-tensor launch: tensor t is cut into chunks of ``chunk`` elements."""
+    pairs = [(t, s0) for t, n in enumerate(numels) for s0 in range(0, n, chunk)]
+    return [t for t, _ in pairs], [s0 for _, s0 in pairs]
+
+
+def _size_tables(numels, chunk, dev):
+    """Device tables (sizes, chunk_tensor, chunk_start) of the tensors with these element counts, and the number of chunks."""
+    ct, cs = _chunk_table(numels, chunk)
+    return (ops.h2d_async(np.asarray(numels, dtype=np.int64), dev), ops.h2d_async(np.asarray(ct, dtype=np.int32), dev),
+            ops.h2d_async(np.asarray(cs, dtype=np.int64), dev), len(ct))
+
+
+class _PtrTable:
+    """Device table of ``n`` pointers, filled through a pinned host buffer and uploaded again only when a pointer changed (the caching
+    allocator usually hands the gradients the same blocks)."""
+
+    def __init__(self, n, dev):
+        self.host = torch.empty(n, dtype=torch.long).pin_memory()
+        self.dev = torch.empty(n, dtype=torch.long, device=dev)
+        self.evt = self.flat = None
+
+    def upload(self, flat):
+        if self.flat != flat:
+            if self.evt is not None:
+                self.evt.synchronize()                              # the previous upload has left the pinned buffer
+            self.host.copy_(torch.tensor(flat, dtype=torch.long))
+            self.dev.copy_(self.host, non_blocking=True)
+            self.evt = torch.cuda.Event(); self.evt.record()
+            self.flat = flat
+
+
+class _StateBlock:
+    """Device block of ``n_words`` 32-bit words: floats, and an int32 counter at ``counter_index``.  It is made at first use and again when
+    the device changes; until then, and into a fresh block, the counter is the host seed (load_state_dict)."""
+
+    def __init__(self, n_words, counter_index):
+        self.n_words, self.k, self.seed, self.dev = n_words, counter_index, 0, None
+
+    def on(self, dev):
+        if self.dev is None or self.dev.device != torch.device(dev):
+            self.dev = torch.zeros(self.n_words, dtype=torch.float32, device=dev)
+            if self.seed:
+                self.set_counter(self.seed)
+        return self.dev
+
+    def counter(self) -> int:                                       # synchronises with the device once the block exists
+        return self.seed if self.dev is None else int(self.dev.view(torch.int32)[self.k])
+
+    def set_counter(self, k: int) -> None:
+        self.seed = int(k)
+        if self.dev is not None:
+            self.dev.view(torch.int32)[self.k:self.k + 1].fill_(self.seed)
+
+    def view(self, i):                                              # 0-dim device tensor (no sync); None before the first use
+        return None if self.dev is None else self.dev[i]
+
+
 class _Plan:
     """Static part of one multi-tensor launch (cached per set of (parameter, hyper-parameters)): sizes, {lr, beta1, beta2, eps} per tensor,
-    chunk table, step-table slots - and the pointer table of its last launch (re-uploaded only when a pointer changed)."""
-    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptr_list", "ptr_host", "ptr_dev", "ptr_evt",
-                 # with an EMA: sizes and chunk table of the "EMA-only" tensors (an average, no gradient in this pattern) and the EMA pointer table
-                 # [n] + [n_only][2], kept like the pointer table above
-                 "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema_list", "ema_host", "ema_dev", "ema_evt")
+    chunk table, step-table slots - and the pointer table of its last launch.  With an EMA also sizes and chunk table of the "EMA-only"
+    tensors (an average, no gradient in this pattern) and the EMA pointer table [n] + [n_only][2]."""
+    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptrs", "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema")
 
 
 class AvAdam(torch.optim.Optimizer):
@@ -119,15 +182,17 @@ class AvAdam(torch.optim.Optimizer):
 
     ``max_grad_norm`` > 0 clips the gradients by their global L2 norm (torch.nn.utils.clip_grad_norm_'s law, taken over the gradients as
     the step sees them: times ``grad_scale``, un-scaled under loss scaling); ``warmup_steps`` / ``total_steps`` scale every group's ``lr``
-    by ``lr_multiplier(k)``, k = steps actually taken.  Both are evaluated on the device by ``av_adam_multi_ex`` (one more read of the
-    gradients for the norm; no host synchronisation, no new plan); ``param_groups[i]["lr"]`` stays the base rate.  All off (the default):
-    the step is ``av_adam_multi``, as before.
+    by ``lr_multiplier(k)``, k = steps actually taken.  Both are evaluated on the device inside the step (one more read of the gradients for
+    the norm; no host synchronisation, no new plan); ``param_groups[i]["lr"]`` stays the base rate.
 
     ``ema_decay`` > 0 keeps ``state[p]["ema"]`` (fp32, created as a copy of ``p`` at the first step in which ``p`` has a gradient; a
     parameter that never gets one has no average: its averaged value is itself): every non-skipped step moves it by
-    ``torch.lerp(ema, p_new, 1 - ema_decay(k))`` inside the Adam launch (``av_adam_multi_ema``), parameters without a gradient in that step
-    included; under loss scaling the device skips it with the step.  ``swap_averaged()`` / ``averaged()`` exchange parameters and averages in
-    place, 16-bit shadows included.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated."""
+    ``torch.lerp(ema, p_new, 1 - ema_decay(k))`` inside the Adam launch, parameters without a gradient in that step included; under loss
+    scaling the device skips it with the step.  ``swap_averaged()`` / ``averaged()`` exchange parameters and averages in place, 16-bit
+    shadows included.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated.
+
+    Every step is one call of ``av_adam_multi_ema`` with zeros and NULLs for what is off: by that function's contract this is
+    ``av_adam_multi_ex`` without an EMA and ``av_adam_multi`` with clipping and schedule off as well - the same kernels are launched."""
 
     SCHEDULE_KEY = "av_schedule_step"     # state_dict entry of the schedule step; torch.optim.Adam.load_state_dict ignores it
     EMA_KEY = "av_ema_step"               # ... of the count of EMA updates
@@ -137,19 +202,18 @@ class AvAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.max_grad_norm, self.warmup_steps, self.total_steps = check_clip_schedule(max_grad_norm, warmup_steps, total_steps)
         self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
-        self._ema_state = None        # device block {decay of the last update, count of updates}, made by the first step
-        self._ema_seed = 0            # count to put into a fresh block (load_state_dict)
+        self._ema_state = _StateBlock(2, ES_K)     # {decay of the last update, count of updates}
         self._swapped = False         # swap_averaged(): the parameters currently hold the averages
         self._swap_plan = None
-        self._clip_state = None       # device block {norm, clip coefficient, lr multiplier, schedule step}, made by the first step
+        self._clip_state = _StateBlock(4, CS_K)    # {norm, clip coefficient, lr multiplier, schedule step}
         self._clip_ws = None          # one double per chunk of all parameters
-        self._sched_seed = 0          # schedule step to put into a fresh block (load_state_dict)
         self.grad_scale = 1.0
         self._plans = {}
         self._slot = None             # id(parameter) -> slot in the device step table
         self._steps_dev = None
         self._steps_seeded = False
-        self.fused_launches = 0       # diagnostics / tests: every step is one av_adam_multi call
+        self._keep = None             # the last step's gradients, alive until the next step (stream-ordered use)
+        self.fused_launches = 0       # diagnostics / tests: every step is one av_adam_multi_ema call
 
     CHUNK = 65536
 
@@ -170,7 +234,6 @@ class AvAdam(torch.optim.Optimizer):
             self._steps_dev = torch.zeros(max(1, len(slots)), dtype=torch.int32, device=dev)
             self._steps_seeded = False
         if not self._steps_seeded:
-            import numpy as np
             host = np.zeros(max(1, len(slots)), dtype=np.int32)
             for group in self.param_groups:
                 for p in group["params"]:
@@ -190,74 +253,46 @@ class AvAdam(torch.optim.Optimizer):
         return self.warmup_steps > 0 or self.total_steps > 0
 
     def _clip_block(self, dev):
-        """State block and norm workspace of av_adam_multi_ex: allocated once, they live with the optimizer."""
-        if self._clip_state is None or self._clip_state.device != torch.device(dev):
-            self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
-            if self._sched_seed:
-                self._clip_state.view(torch.int32)[3:4].fill_(self._sched_seed)
-            self._clip_ws = None
-        if self._clip_ws is None:
+        """State block and norm workspace of clipping and schedule: allocated once, they live with the optimizer."""
+        cstate = self._clip_state.on(dev)
+        if self._clip_ws is None or self._clip_ws.device != cstate.device:
             nch = sum(-(-p.numel() // self.CHUNK) for group in self.param_groups for p in group["params"])
             self._clip_ws = torch.empty(max(1, nch), dtype=torch.float64, device=dev)
-        return self._clip_state, self._clip_ws
-
-    def _clip_view(self, i):
-        return None if self._clip_state is None else self._clip_state[i]
+        return cstate, self._clip_ws
 
     @property
     def last_grad_norm(self):
         """0-dim device tensor (a view of the state block, no sync): global L2 norm of the last step's gradients as Adam saw them.  None
         before the first step with clipping or a schedule on; 0 with clipping off."""
-        return self._clip_view(0)
+        return self._clip_state.view(CS_NORM)
 
     @property
     def last_clip_coef(self):
         """0-dim device tensor: min(1, max_grad_norm / (norm + 1e-6)) of the last step."""
-        return self._clip_view(1)
+        return self._clip_state.view(CS_COEF)
 
     @property
     def last_lr_mult(self):
         """0-dim device tensor: learning-rate multiplier the last step ran at."""
-        return self._clip_view(2)
+        return self._clip_state.view(CS_LRM)
 
     def schedule_step(self) -> int:
         """Steps taken on the schedule so far (synchronises with the device; checkpoints and diagnostics, like AvGradScaler.steps_taken)."""
-        if self._clip_state is None:
-            return self._sched_seed
-        return int(self._clip_state.view(torch.int32)[3])
-
-    def _set_schedule_step(self, k: int) -> None:
-        self._sched_seed = int(k)
-        if self._clip_state is not None:
-            self._clip_state.view(torch.int32)[3:4].fill_(self._sched_seed)
+        return self._clip_state.counter()
 
     @property
     def averaging(self) -> bool:
         return self.ema_decay > 0.0
 
-    def _ema_block(self, dev):
-        if self._ema_state is None or self._ema_state.device != torch.device(dev):
-            self._ema_state = torch.zeros(2, dtype=torch.float32, device=dev)
-            if self._ema_seed:
-                self._ema_state.view(torch.int32)[1:2].fill_(self._ema_seed)
-        return self._ema_state
-
     @property
     def last_ema_decay(self):
         """0-dim device tensor (a view of the EMA state block, no sync): decay d_k the last step's EMA update ran at.  None before the
         first step with an EMA."""
-        return None if self._ema_state is None else self._ema_state[0]
+        return self._ema_state.view(ES_DECAY)
 
     def ema_step(self) -> int:
         """EMA updates made so far (synchronises with the device, like schedule_step)."""
-        if self._ema_state is None:
-            return self._ema_seed
-        return int(self._ema_state.view(torch.int32)[1])
-
-    def _set_ema_step(self, k: int) -> None:
-        self._ema_seed = int(k)
-        if self._ema_state is not None:
-            self._ema_state.view(torch.int32)[1:2].fill_(self._ema_seed)
+        return self._ema_state.counter()
 
     def _averaged_params(self):
         return [p for group in self.param_groups for p in group["params"] if "ema" in self.state.get(p, ())]
@@ -272,21 +307,15 @@ class AvAdam(torch.optim.Optimizer):
         self._swapped = not self._swapped
         if not ps:
             return
-        import numpy as np
         dev = ps[0].device
         shadows = shadow.lookup_many(ps)
         flat = []
         for p, sh in zip(ps, shadows):
             flat += [p.data_ptr(), self.state[p]["ema"].data_ptr(), sh.data_ptr() if sh is not None else 0]
-        key = (tuple(flat), tuple(p.numel() for p in ps))
+        numels = [p.numel() for p in ps]
+        key = (tuple(flat), tuple(numels))
         if self._swap_plan is None or self._swap_plan[0] != key:
-            ct, cs = [], []
-            for t, p in enumerate(ps):
-                for s0 in range(0, p.numel(), self.CHUNK):
-                    ct.append(t); cs.append(s0)
-            self._swap_plan = (key, ops.h2d_async(np.asarray(flat, dtype=np.int64), dev),
-                               ops.h2d_async(np.asarray([p.numel() for p in ps], dtype=np.int64), dev),
-                               ops.h2d_async(np.asarray(ct, dtype=np.int32), dev), ops.h2d_async(np.asarray(cs, dtype=np.int64), dev), len(ct))
+            self._swap_plan = (key, ops.h2d_async(np.asarray(flat, dtype=np.int64), dev), *_size_tables(numels, self.CHUNK, dev))
         _, ptrs, sizes, ct, cs, nch = self._swap_plan
         L.check(L.lib().av_param_swap_multi(ops.ptr(ptrs), ops.ptr(sizes), ops.ptr(ct), ops.ptr(cs), nch, self.CHUNK, ops.stream()),
                 "av_param_swap_multi")
@@ -304,8 +333,8 @@ class AvAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._set_schedule_step(state_dict.get(self.SCHEDULE_KEY, 0))
-        self._set_ema_step(state_dict.get(self.EMA_KEY, 0))
+        self._clip_state.set_counter(state_dict.get(self.SCHEDULE_KEY, 0))
+        self._ema_state.set_counter(state_dict.get(self.EMA_KEY, 0))
         for st in self.state.values():                              # torch >= 2 stores 'step' as a tensor in its own checkpoints
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"])
@@ -316,8 +345,8 @@ class AvAdam(torch.optim.Optimizer):
         self.state.clear()
         self._steps_seeded = False
         self._keep = None
-        self._set_schedule_step(0)
-        self._set_ema_step(0)
+        self._clip_state.set_counter(0)
+        self._ema_state.set_counter(0)
         self._swapped = False
 
     def state_dict(self):
@@ -350,37 +379,18 @@ class AvAdam(torch.optim.Optimizer):
             key = (key, tuple((p.data_ptr(), p.numel()) for p in ema_only))
         pl = self._plans.get(key)
         if pl is None:
-            import numpy as np
             if len(self._plans) >= 64:                              # LayerDrop patterns: a handful of distinct parameter sets
                 self._plans.clear()
             pl = _Plan()
-            ct, cs = [], []
-            for t, (p, _, _) in enumerate(plist):
-                for s0 in range(0, p.numel(), self.CHUNK):
-                    ct.append(t); cs.append(s0)
-            pl.sizes = ops.h2d_async(np.asarray([p.numel() for p, _, _ in plist], dtype=np.int64), dev)
+            pl.n = len(plist)
+            pl.sizes, pl.ct, pl.cs, pl.nch = _size_tables([p.numel() for p, _, _ in plist], self.CHUNK, dev)
             pl.hyper = ops.h2d_async(np.asarray([hp for _, hp, _ in plist], dtype=np.float32).reshape(-1, 4), dev)
-            pl.ct = ops.h2d_async(np.asarray(ct, dtype=np.int32), dev)
-            pl.cs = ops.h2d_async(np.asarray(cs, dtype=np.int64), dev)
             pl.slots = ops.h2d_async(np.asarray([slots[id(p)] for p, _, _ in plist], dtype=np.int32), dev)
-            pl.nch, pl.n = len(ct), len(plist)
-            pl.ptr_list = pl.ptr_evt = None
-            pl.ptr_host = torch.empty(5 * len(plist), dtype=torch.long).pin_memory()
-            pl.ptr_dev = torch.empty(5 * len(plist), dtype=torch.long, device=dev)
-            if ema_only is not None:
-                ct, cs = [], []
-                for t, p in enumerate(ema_only):
-                    for s0 in range(0, p.numel(), self.CHUNK):
-                        ct.append(t); cs.append(s0)
-                pl.eo_n, pl.eo_nch = len(ema_only), len(ct)
-                pl.eo_sizes = pl.eo_ct = pl.eo_cs = None
-                if ema_only:
-                    pl.eo_sizes = ops.h2d_async(np.asarray([p.numel() for p in ema_only], dtype=np.int64), dev)
-                    pl.eo_ct = ops.h2d_async(np.asarray(ct, dtype=np.int32), dev)
-                    pl.eo_cs = ops.h2d_async(np.asarray(cs, dtype=np.int64), dev)
-                pl.ema_list = pl.ema_evt = None
-                pl.ema_host = torch.empty(len(plist) + 2 * len(ema_only), dtype=torch.long).pin_memory()
-                pl.ema_dev = torch.empty(len(plist) + 2 * len(ema_only), dtype=torch.long, device=dev)
+            pl.ptrs = _PtrTable(5 * pl.n, dev)
+            pl.eo_n = len(ema_only or ())
+            pl.eo_sizes, pl.eo_ct, pl.eo_cs, pl.eo_nch = (_size_tables([p.numel() for p in ema_only], self.CHUNK, dev) if pl.eo_n
+                                                          else (None, None, None, 0))
+            pl.ema = _PtrTable(pl.n + 2 * pl.eo_n, dev) if ema_only is not None else None
             self._plans[key] = pl
         return pl
 
@@ -398,13 +408,11 @@ class AvAdam(torch.optim.Optimizer):
                 if st and "step" in st:
                     st["step"] = int(host[slots[id(p)]])
 
-    def step(self, closure=None, scaler: "AvGradScaler" = None):
-        """One fused multi-tensor launch for all parameters that have a gradient (per-tensor step counts, per-group lr / betas / eps)."""
-        if self._swapped:
-            raise RuntimeError("AvAdam.step: the parameters hold the averaged weights (swap_averaged); swap back before stepping")
-        loss = closure() if closure is not None else None
+    def _collect(self):
+        """(plist, ema_only): (parameter, {lr, beta1, beta2, eps}, state) of every parameter with a gradient, its state created at its
+        first step; with an EMA, the parameters that have an average and no gradient in this step (still moved towards p), else None."""
         plist = []
-        ema_only = [] if self.averaging else None                   # an average, no gradient in this step: still moved towards p
+        ema_only = [] if self.averaging else None
         for group in self.param_groups:
             b1, b2 = group["betas"]
             hp = (float(group["lr"]), float(b1), float(b2), float(group["eps"]))
@@ -423,58 +431,58 @@ class AvAdam(torch.optim.Optimizer):
                 if ema_only is not None and "ema" not in state:
                     state["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
                 plist.append((p, hp, state))
-        if not plist:
-            return loss
-        dev = plist[0][0].device
-        steps = self._step_table(dev)                               # BEFORE the host counts move: a fresh table is seeded from them
-        pl = self._plan(plist, dev, ema_only)
-        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p, _, _ in plist]
-        shadows = shadow.lookup_many([p for p, _, _ in plist])  # bf16 compute copies (perf path), written by the kernel
+        return plist, ema_only
+
+    def _bind(self, pl, plist, ema_only, grads, shadows) -> None:
+        """This step's pointers into the plan's tables: {param, grad, exp_avg, exp_avg_sq, shadow} per tensor and, with an EMA, the
+        averages of those tensors followed by {param, ema} of the EMA-only ones."""
         flat = []
         for (p, _, st), g, sh in zip(plist, grads, shadows):
             flat += [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), sh.data_ptr() if sh is not None else 0]
-        if pl.ptr_list != flat:                                     # the caching allocator usually hands the gradients the same blocks
-            if pl.ptr_evt is not None:
-                pl.ptr_evt.synchronize()                            # the previous upload has left the pinned buffer
-            pl.ptr_host.copy_(torch.tensor(flat, dtype=torch.long))
-            pl.ptr_dev.copy_(pl.ptr_host, non_blocking=True)
-            pl.ptr_evt = torch.cuda.Event(); pl.ptr_evt.record()
-            pl.ptr_list = flat
-        args = [ops.ptr(pl.ptr_dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch, self.CHUNK, ops.ptr(steps),
-                ops.ptr(pl.slots), pl.n, float(self.grad_scale)]
-        if scaler is not None:
-            args += [ops.ptr(scaler.state), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval]
-        else:
-            args += [None, 1.0, 1.0, 1]
-        if self.averaging:
+        pl.ptrs.upload(flat)
+        if pl.ema is not None:
             eflat = [st["ema"].data_ptr() for _, _, st in plist]
             for p in ema_only:
                 eflat += [p.data_ptr(), self.state[p]["ema"].data_ptr()]
-            if pl.ema_list != eflat:
-                if pl.ema_evt is not None:
-                    pl.ema_evt.synchronize()
-                pl.ema_host.copy_(torch.tensor(eflat, dtype=torch.long))
-                pl.ema_dev.copy_(pl.ema_host, non_blocking=True)
-                pl.ema_evt = torch.cuda.Event(); pl.ema_evt.record()
-                pl.ema_list = eflat
-            cstate, ws = self._clip_block(dev) if self.clipping or self.scheduled else (None, None)
-            only = pl.ema_dev.data_ptr() + 8 * pl.n if pl.eo_n else None
-            L.check(L.lib().av_adam_multi_ema(*args, self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
-                                              ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), ops.ptr(pl.ema_dev),
-                                              only, ops.ptr(pl.eo_sizes), ops.ptr(pl.eo_ct), ops.ptr(pl.eo_cs), pl.eo_nch, self.ema_decay,
-                                              int(self.ema_warmup), ops.ptr(self._ema_block(dev)), ops.stream()), "av_adam_multi_ema")
-        elif self.clipping or self.scheduled:
-            cstate, ws = self._clip_block(dev)
-            L.check(L.lib().av_adam_multi_ex(*args, self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
-                                             ws.numel() * ws.element_size(), ops.ptr(cstate), ops.stream()), "av_adam_multi_ex")
-        else:
-            L.check(L.lib().av_adam_multi(*args, ops.stream()), "av_adam_multi")
+            pl.ema.upload(eflat)
+
+    def _launch(self, pl, steps, scaler, dev) -> None:
+        """The one native call of a step.  Whatever is off is passed as zeros and NULLs."""
+        scale = (None, 1.0, 1.0, 1) if scaler is None else (ops.ptr(scaler.state), scaler.growth_factor, scaler.backoff_factor,
+                                                            scaler.growth_interval)
+        cstate, ws = self._clip_block(dev) if self.clipping or self.scheduled else (None, None)
+        ema = (None, None, None, None, None, 0, 0.0, 0, None)
+        if self.averaging:
+            only = pl.ema.dev.data_ptr() + 8 * pl.n if pl.eo_n else None
+            ema = (ops.ptr(pl.ema.dev), only, ops.ptr(pl.eo_sizes), ops.ptr(pl.eo_ct), ops.ptr(pl.eo_cs), pl.eo_nch, self.ema_decay,
+                   int(self.ema_warmup), ops.ptr(self._ema_state.on(dev)))
+        L.check(L.lib().av_adam_multi_ema(ops.ptr(pl.ptrs.dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
+                                          self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), *scale,
+                                          self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
+                                          ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), *ema, ops.stream()),
+                "av_adam_multi_ema")
+        self.fused_launches += 1
+
+    def step(self, closure=None, scaler: "AvGradScaler" = None):
+        """One fused multi-tensor launch for all parameters that have a gradient (per-tensor step counts, per-group lr / betas / eps)."""
+        if self._swapped:
+            raise RuntimeError("AvAdam.step: the parameters hold the averaged weights (swap_averaged); swap back before stepping")
+        loss = closure() if closure is not None else None
+        plist, ema_only = self._collect()
+        if not plist:
+            return loss
+        params = [p for p, _, _ in plist]
+        dev = params[0].device
+        steps = self._step_table(dev)                               # BEFORE the host counts move: a fresh table is seeded from them
+        pl = self._plan(plist, dev, ema_only)
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
+        shadows = shadow.lookup_many(params)                        # bf16 compute copies (perf path), written by the kernel
+        self._bind(pl, plist, ema_only, grads, shadows)
+        self._launch(pl, steps, scaler, dev)
         if scaler is None:
             for _, _, st in plist:                                  # exact host mirror (with a scaler the device decides: sync_steps)
                 st["step"] = int(st["step"]) + 1
-        self.fused_launches += 1
-        self._keep = grads                                      # alive until the next step (stream-ordered use)
-        params = [p for p, _, _ in plist]
-        torch.autograd.graph.increment_version(params)          # other compute-dtype caches (re-layouts) rebuild
+        self._keep = grads                                          # alive until the next step (stream-ordered use)
+        torch.autograd.graph.increment_version(params)              # other compute-dtype caches (re-layouts) rebuild
         shadow.mark_fresh([p for p, sh in zip(params, shadows) if sh is not None])      # ... the shadows were just written
         return loss

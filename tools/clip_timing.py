@@ -1,10 +1,10 @@
 """The fused Adam step with global-norm clipping and the learning-rate schedule on one MI355X, on the trainable tensor set of the headline
 configuration (wav2vec2-large layers 6-9, fusion, CTC head: the shapes of the parameters with requires_grad, random values), against the
 plain step and against the only form available before:
-  (a) av_adam_multi                                       (AvAdam, everything off),
-  (b) av_adam_multi_ex with clipping and schedule         (AvAdam(max_grad_norm=1.0, warmup_steps=10, total_steps=1000)),
+  (a) the plain step                                      (AvAdam, everything off),
+  (b) the step with clipping and schedule                 (AvAdam(max_grad_norm=1.0, warmup_steps=10, total_steps=1000)),
   (c) torch.nn.utils.clip_grad_norm_ followed by (a).
-Alternating triples in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
+Every side is one av_adam_multi_ema call, with zeros for what is off.  Alternating triples in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
 profiles/adam_clip_timing.txt; records, gates nothing.
 
     python tools/clip_timing.py [--out profiles/adam_clip_timing.txt] [--rounds 30]
@@ -94,8 +94,8 @@ def main():
     lines = [f"# tools/clip_timing.py on {torch.cuda.get_device_name(0)}.  {len(shapes)} trainable tensors of the headline configuration, "
              f"{n_el / 1e6:.1f} M elements ({gb:.3f} GB of fp32 gradients), {sum(-(-torch.Size(s).numel() // oa.CHUNK) for s in shapes)} chunks.",
              f"# {args.rounds} alternating rounds (a, b, c) after 5 warm-up rounds, device events around each side, no bf16 shadows.",
-             f"  (a) av_adam_multi                               {fmt(a_ms)}   ~{7 * gb:.2f} GB moved (read p g m v, write p m v)",
-             f"  (b) av_adam_multi_ex, clipping + schedule       {fmt(b_ms)}   ~{8 * gb:.2f} GB moved ((a) + one read of g)",
+             f"  (a) plain step                                  {fmt(a_ms)}   ~{7 * gb:.2f} GB moved (read p g m v, write p m v)",
+             f"  (b) step with clipping + schedule               {fmt(b_ms)}   ~{8 * gb:.2f} GB moved ((a) + one read of g)",
              f"  (c) clip_grad_norm_ then (a)                    {fmt(c_ms)}   ~{10 * gb:.2f} GB moved ((a) + read g, read g, write g)",
              f"  (b) - (a) {bm - am:.3f} ms = one read of the gradients at {gb / max(bm - am, 1e-9) * 1e3:.0f} GB/s plus two small launches;  "
              f"(b) / (c) x{bm / cm:.3f};  (b) ahead of (c) in {wins} of {args.rounds} rounds",

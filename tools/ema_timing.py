@@ -1,11 +1,11 @@
 """The fused Adam step with the weight EMA on one MI355X, on the trainable tensor set of the headline configuration (wav2vec2-large layers
 6-9, fusion, CTC head: the shapes of the parameters with requires_grad, random values), against the plain step and against the only form
 available before:
-  (a) av_adam_multi                                       (AvAdam, everything off),
-  (b) av_adam_multi_ema                                   (AvAdam(ema_decay=0.999): the average moves inside the Adam launch),
+  (a) the plain step                                      (AvAdam, everything off),
+  (b) the step with the EMA                               (AvAdam(ema_decay=0.999): the average moves inside the Adam launch),
   (c) (a) followed by torch._foreach_lerp_ over cloned EMA tensors (what torch.optim.swa_utils.AveragedModel runs after the step; blind to
       skipped steps and to the 16-bit shadows).
-Also (d), av_param_swap_multi: one exchange of parameters and averages, as evaluate() with eval_ema pays twice per call.
+(a) and (b) are the same native call, av_adam_multi_ema, with and without a decay.  Also (d), av_param_swap_multi: one exchange of parameters and averages, as evaluate() with eval_ema pays twice per call.
 Alternating rounds in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
 profiles/adam_ema_timing.txt; records, gates nothing.
 
@@ -74,9 +74,9 @@ def main():
     lines = [f"# tools/ema_timing.py on {torch.cuda.get_device_name(0)}.  {len(shapes)} trainable tensors of the headline configuration, "
              f"{n_el / 1e6:.1f} M elements ({gb:.3f} GB per fp32 copy), {sum(-(-torch.Size(s).numel() // oa.CHUNK) for s in shapes)} chunks.",
              f"# {args.rounds} alternating rounds (a, b, c) after 5 warm-up rounds, device events around each side, no bf16 shadows.",
-             f"  (a) av_adam_multi                               {fmt(a_ms)}   28 B/element = {7 * gb:.2f} GB moved (read p g m v, write p m v; "
+             f"  (a) plain step                                  {fmt(a_ms)}   28 B/element = {7 * gb:.2f} GB moved (read p g m v, write p m v; "
              f"30 B with a 16-bit shadow)",
-             f"  (b) av_adam_multi_ema, decay 0.999              {fmt(b_ms)}   36 B/element = {9 * gb:.2f} GB moved ((a) + read and write ema; "
+             f"  (b) step with the EMA, decay 0.999              {fmt(b_ms)}   36 B/element = {9 * gb:.2f} GB moved ((a) + read and write ema; "
              f"38 B with a shadow)",
              f"  (c) (a) then torch._foreach_lerp_               {fmt(c_ms)}   40 B/element = {10 * gb:.2f} GB moved ((a) + read p, read and write ema; "
              f"42 B with a shadow)",
