@@ -409,6 +409,33 @@ int av_ctc_align(const float* log_probs, long long stride_b, long long stride_t,
                  const long long* input_lengths, const long long* target_lengths, int B, int T, int V, int S_max, int blank,
                  int* out_state, int* out_span, float* out_token_score, float* out_score, void* workspace, long long workspace_bytes,
                  void* stream);
+/* CTC confidences on the device (csrc/ctc_confidence.hip; the entropy-based frame confidence of Laptev & Ginsburg 2022 and its
+ * aggregation over a token's frames): fp32, no atomics, no synchronisation, lengths read from DEVICE memory (NULL: T), clamped to [0, T].
+ * Frame law for a row x[0..V), m = max x, d = x - m, e = exp(d), s = sum e (it renormalises):
+ *   AV_CONF_MAX_PROB  c = (V / s - 1) / (V - 1)
+ *   AV_CONF_ENTROPY   c = 1 + (sum_{e > 0} e d / s - ln s) / ln V
+ *   AV_CONF_TSALLIS   c = (sum exp(alpha d) / exp(alpha ln s) - u) / (1 - u), u = exp((1 - alpha) ln V); alpha finite, > 0, |alpha - 1| >= 1/64
+ * result c >= 0 ? min(c, 1) : 0; a NaN entry, a row without a finite maximum and every frame t >= T_b give 0.
+ * av_ctc_frame_conf: log_probs and strides as for av_ctc_align, V >= 2, 1 <= T <= 4096 -> conf fp32 [B][T].
+ * av_ctc_span_conf: conf fp32 [B][T], spans int32 [B][L][2] (first frame, end exclusive; clipped to [0, T_b)) -> token_conf fp32 [B][L]:
+ *   AV_AGG_MEAN the fp32 sum in frame order divided once by the count, AV_AGG_MIN the minimum, AV_AGG_PROD the fp32 product in frame
+ *   order; 0 for a span of -1 and for one that is empty after clipping.  L = 0: nothing is launched.
+ * av_ctc_greedy_timed: ONE read of log_probs for av_ctc_greedy's out_ids / out_len, the run of equal argmax frames behind every emitted
+ *   id (out_span int32 [B][T][2], -1 padded: the spans av_ctc_align finds for these ids), av_ctc_span_conf over those runs (token_conf
+ *   fp32 [B][T], 0 padded) and av_ctc_frame_conf (frame_conf fp32 [B][T]); the two agree with the separate calls bit for bit. */
+#define AV_CONF_MAX_PROB 0
+#define AV_CONF_ENTROPY 1
+#define AV_CONF_TSALLIS 2
+#define AV_AGG_MEAN 0
+#define AV_AGG_MIN 1
+#define AV_AGG_PROD 2
+int av_ctc_frame_conf(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int B, int T, int V,
+                      int method, float alpha, float* conf, void* stream);
+int av_ctc_span_conf(const float* conf, const int* spans, const long long* lengths, int B, int T, int L, int aggregation,
+                     float* token_conf, void* stream);
+int av_ctc_greedy_timed(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int B, int T, int V,
+                        int blank, int method, float alpha, int aggregation, int* out_ids, int* out_len, int* out_span,
+                        float* token_conf, float* frame_conf, void* stream);
 /* Word, character and token error counts on the device: edit distance with operation counts between ONE reference and N hypotheses per
  * utterance, from token ids through a device copy of the tokenizer's piece table - what MultimodalTrainer.evaluate() measures
  * (word_error_rate of model/trainer.py, the jiwer.wer stand-in), plus the character and token levels and the S / D / I breakdown.

@@ -16,6 +16,8 @@ AV_F32, AV_BF16 = 0, 1
 A_ROWMAJOR, A_TRANS, A_CONV2D, A_CONV3D1 = 0, 1, 2, 3
 B_NK, B_KN = 0, 1
 ACT_NONE, ACT_GELU, ACT_MUL_GELU_GRAD, ACT_GELU_GF, ACT_MUL_AUX = 0, 1, 2, 3, 4
+CONF_METHODS = {"max_prob": 0, "entropy": 1, "tsallis": 2}        # AV_CONF_*
+CONF_AGGREGATIONS = {"mean": 0, "min": 1, "prod": 2}             # AV_AGG_*
 LSTM_COUNTER_INTS = 1024         # AV_LSTM_COUNTER_INTS: device workspace of av_lstm_*_layer
 
 vp, ll, i32, f32 = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -142,6 +144,9 @@ SIGNATURES = {
     "av_ctc_nbest_bwd": [vp, ll, ll, vp, ll, ll, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "av_ctc_align_workspace_bytes": [i32, i32, i32, C.POINTER(ll)],
     "av_ctc_align": [vp, ll, ll, vp, ll, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, ll, vp],
+    "av_ctc_frame_conf": [vp, ll, ll, vp, i32, i32, i32, i32, f32, vp, vp],
+    "av_ctc_span_conf": [vp, vp, vp, i32, i32, i32, i32, vp, vp],
+    "av_ctc_greedy_timed": [vp, ll, ll, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp],
     "av_error_counts_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(ll)],
     "av_error_counts": [vp, ll, vp, vp, ll, ll, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, ll, vp],
     "av_augment_lips": [vp, vp, vp, i32, i32, i32, i32, C.c_ulonglong, ll, C.c_uint, i32, i32, i32, i32, vp],

@@ -147,16 +147,23 @@ def token_path(alignment: Alignment, targets: torch.Tensor, blank: int) -> torch
     return torch.where(st < 0, torch.full_like(st, -1), ids)
 
 
-def word_segments(tokenizer, target_ids, spans, token_scores, frame_rate: float = 25.0) -> List[dict]:
+def word_segments(tokenizer, target_ids, spans, token_scores, frame_rate: float = 25.0, token_conf=None, aggregation: str = "min") -> List[dict]:
     """Word times of ONE utterance (host).  ``target_ids``: its L label ids; ``spans`` [>= L, 2] and ``token_scores`` [>= L] as returned by
     ``forced_align`` for it.  Words are the maximal runs of tokens between '▁' pieces (utils/tokenizer.py); each is a dict with ``word``,
     ``start`` = first token's first frame / frame_rate, ``end`` = last token's end frame / frame_rate (seconds), ``score`` = mean token
-    score per frame of the word.  An infeasible utterance (a span of -1) gives []."""
+    score per frame of the word.  An infeasible utterance (a span of -1) gives [].  With ``token_conf`` [>= L] (confidence.py) every word
+    also has ``confidence``: the ``aggregation`` ("mean", "min", "prod"; confidence.py's span law in float32) of its tokens' confidences."""
     ids = [int(i) for i in (target_ids.tolist() if hasattr(target_ids, "tolist") else target_ids)]
     sp = np.asarray(spans.cpu() if isinstance(spans, torch.Tensor) else spans).reshape(-1, 2)[:len(ids)]
     sc = np.asarray(token_scores.cpu() if isinstance(token_scores, torch.Tensor) else token_scores, dtype=np.float64).reshape(-1)[:len(ids)]
     if len(sp) < len(ids) or len(sc) < len(ids) or (sp < 0).any():
         return []
+    if token_conf is not None:
+        from .confidence import check_aggregation, host_span_law
+        check_aggregation("word_segments", aggregation)
+        tc = np.asarray(token_conf.cpu() if isinstance(token_conf, torch.Tensor) else token_conf, dtype=np.float32).reshape(-1)[:len(ids)]
+        if len(tc) < len(ids):
+            raise ValueError(f"word_segments: token_conf holds {len(tc)} values for {len(ids)} tokens")
     space = tokenizer.token_to_id.get("▁")
     words, run = [], []
 
@@ -166,6 +173,8 @@ def word_segments(tokenizer, target_ids, spans, token_scores, frame_rate: float 
             words.append({"word": "".join(tokenizer.id_to_token[ids[j]] if 0 <= ids[j] < tokenizer.vocab_size else "" for j in run),
                           "start": int(sp[run[0], 0]) / frame_rate, "end": int(sp[run[-1], 1]) / frame_rate,
                           "score": float(sum(sc[j] for j in run) / max(frames, 1))})
+            if token_conf is not None:
+                words[-1]["confidence"] = float(host_span_law(tc[run], 0, len(run), len(run), aggregation))
             del run[:]
     for j, i in enumerate(ids):
         if i == space:

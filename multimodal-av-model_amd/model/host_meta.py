@@ -41,6 +41,37 @@ def fusion_lengths_host(mask_cpu: torch.Tensor, T_enc: int, Tv: int) -> torch.Te
     return torch.from_numpy((j[None, :] < n[:, None]).sum(1).astype(np.int64))
 
 
+AUDIO_PER_LIP_FRAME = 640            # waveform samples per lip frame: 16 kHz / 25 frames per second
+
+
+def inference_masks(n_audio, n1, n2, width: int):
+    """(mask1, mask2), int64 [B, width], for a mixture that comes without the two clean clips the dataset builds its masks from: per item
+    the mixture holds ``n_audio`` samples, speaker k speaks during the first ``n_k``.  For speaker k: 1 where t < min(n1, n2) (both
+    speak), 2 where min(n1, n2) <= t < n_k (only this speaker), 0 up to n_audio, 3 beyond - the law of the reference's mixing
+    (oracle/pipeline_oracle.py mix_pair) plus the collate's pad code.  Lengths are clamped to [0, width] and n_k to n_audio."""
+    na = np.clip(np.asarray(n_audio, np.int64).reshape(-1), 0, width)
+    a, b = (np.minimum(np.clip(np.asarray(n, np.int64).reshape(-1), 0, width), na) for n in (n1, n2))
+    if not na.shape == a.shape == b.shape:
+        raise ValueError(f"inference_masks: need one length per item, got {na.shape[0]}, {a.shape[0]} and {b.shape[0]}")
+    t = np.arange(width, dtype=np.int64)[None, :]
+    both = np.minimum(a, b)[:, None]
+    out = []
+    for n in (a, b):
+        m = np.where(t < both, 1, np.where(t < n[:, None], 2, np.where(t < na[:, None], 0, 3)))
+        out.append(torch.from_numpy(m.astype(np.int64)))
+    return tuple(out)
+
+
+def batch_inference_masks(batch: Dict[str, torch.Tensor]):
+    """``inference_masks`` from what an unlabeled batch carries: ``audio`` [B, width], optionally ``audio_lengths`` (default: the full width)
+    and ``lip{k}_lengths`` in lip frames (x 640 samples, clamped to the audio; default: the audio's length)."""
+    B, width = batch["audio"].shape
+    host = lambda t: torch.as_tensor(t).cpu().long().numpy()                  # noqa: E731
+    na = host(batch["audio_lengths"]) if "audio_lengths" in batch else np.full(B, width, np.int64)
+    n1, n2 = (host(batch[k]) * AUDIO_PER_LIP_FRAME if k in batch else na for k in ("lip1_lengths", "lip2_lengths"))
+    return inference_masks(na, n1, n2, width)
+
+
 def host_metadata(cpu_batch: Dict[str, torch.Tensor], T_enc: int) -> Dict[str, object]:
     """Everything the step would otherwise read back from the device: contrastive class counts and the CTC length vectors
     (nn.functional.ctc_loss wants its lengths on the host; handing it device tensors costs a full device synchronisation per call).

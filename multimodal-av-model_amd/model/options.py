@@ -47,6 +47,11 @@ OPTIONS = {
     "ema_decay": ("AVAMD_EMA_DECAY", float, "0", float),
     "ema_warmup": ("AVAMD_EMA_WARMUP", _is1, "0", bool),
     "eval_ema": ("AVAMD_EVAL_EMA", _is1, "0", bool),
+    # transcribe()'s confidences (confidence.py): the frame measure ("tsallis", "entropy", "max_prob"), the Tsallis exponent, and how a token's
+    # frames, a word's tokens and an utterance's tokens are aggregated ("min", "mean", "prod"); read by transcribe() alone
+    "conf_method": ("AVAMD_CONF_METHOD", str, "tsallis", str),
+    "conf_alpha": ("AVAMD_CONF_ALPHA", float, "0.33", float),
+    "conf_aggregation": ("AVAMD_CONF_AGG", str, "min", str),
 }
 
 
@@ -68,6 +73,12 @@ def check_mwer(weight: float, nbest: int, beam: int, level: str) -> None:
         raise ValueError(f"need 1 <= mwer_nbest <= mwer_beam <= 64, got mwer_nbest={nbest} mwer_beam={beam}")
     if level not in ("word", "char", "token"):
         raise ValueError(f"mwer_level must be 'word', 'char' or 'token', got {level!r}")
+
+
+def check_confidence(method: str, alpha: float, aggregation: str) -> None:
+    from ..confidence import check_aggregation, check_method
+    check_method("conf_method / conf_alpha", method, alpha)
+    check_aggregation("conf_aggregation", aggregation)
 
 
 def check_ema(eval_ema: bool, ema_decay: float) -> None:

@@ -70,7 +70,8 @@ class MultimodalTrainer:
                  eval_bias_weight: Optional[float] = None, mwer_weight: Optional[float] = None, mwer_nbest: Optional[int] = None,
                  mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
-                 ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None):
+                 ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None, conf_method: Optional[str] = None,
+                 conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -90,6 +91,9 @@ class MultimodalTrainer:
         self.native_ctc = opt("native_ctc", native_ctc)
         self._resolve_decode(eval_beam_width, eval_lm, eval_lm_weight, eval_token_bonus, eval_bias, eval_bias_weight)
         self.eval_report, self.last_report = opt("eval_report", eval_report), None
+        self.conf_method, self.conf_alpha = opt("conf_method", conf_method), opt("conf_alpha", conf_alpha)
+        self.conf_aggregation = opt("conf_aggregation", conf_aggregation)
+        options.check_confidence(self.conf_method, self.conf_alpha, self.conf_aggregation)
         self.mwer_weight, self.mwer_nbest = opt("mwer_weight", mwer_weight), opt("mwer_nbest", mwer_nbest)
         self.mwer_beam, self.mwer_level = opt("mwer_beam", mwer_beam), mwer_level
         options.check_mwer(self.mwer_weight, self.mwer_nbest, self.mwer_beam, mwer_level)
@@ -172,7 +176,8 @@ class MultimodalTrainer:
     def _to_dev(self, batch):
         dev = self.device
         nb = lambda t: t.to(dev, non_blocking=True)
-        d = {k: nb(batch[k]) for k in ("audio", "mask1", "mask2", "text1", "text2", "text1_lengths", "text2_lengths")}
+        d = {k: nb(batch[k]) for k in ("audio", "mask1", "mask2")}
+        d.update((k, nb(batch[k])) for k in ("text1", "text2", "text1_lengths", "text2_lengths") if k in batch)    # an unlabeled batch has none
         # [B,T,1,H,W] -> [B,1,T,H,W]: with one channel the two layouts are byte-identical => a view
         d["lip1"] = nb(batch["lip1"]).permute(0, 2, 1, 3, 4)
         d["lip2"] = nb(batch["lip2"]).permute(0, 2, 1, 3, 4)
@@ -220,6 +225,22 @@ class MultimodalTrainer:
         out.update(visual_feat1=vf1, visual_feat2=vf2, audio_last=a1, audio_mid=mid1, fused1=f1, fused2=f2, input_lengths1=il1,
                    input_lengths2=il2, log_probs1=lp1, log_probs2=lp2, loss1=l1, loss2=l2, contrast1=c1, contrast2=c2, total=total)
         return out
+
+    def forward_log_probs(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """forward_losses without a transcript: the same stages up to the CTC head, no loss and no contrastive term.  ``batch`` needs
+        ``audio``, ``lip1`` and ``lip2``; the ``text*`` keys are not read, and where ``mask1`` / ``mask2`` are missing they are built on the
+        host from the optional ``audio_lengths`` / ``lip*_lengths`` (host_meta.batch_inference_masks)."""
+        if "mask1" not in batch or "mask2" not in batch:
+            m1, m2 = host_meta.batch_inference_masks(batch)
+            batch = {**batch, "mask1": m1, "mask2": m2}
+        d = self._inputs(batch)
+        vf1, vf2, join = self._lips(d)
+        a1, _, a2, _ = self._audio(d, batch)
+        T_enc = a1.shape[1]
+        m1, m2 = self._mask_ds(d["mask1"], T_enc), self._mask_ds(d["mask2"], T_enc)
+        join()
+        _, _, il1, il2, lp1, lp2, _, _ = self._heads(vf1, vf2, a1, a2, m1, m2)
+        return dict(log_probs1=lp1, log_probs2=lp2, input_lengths1=il1, input_lengths2=il2)
 
     def _inputs(self, batch):
         """Main stream: the batch's device copy and, in a training step with ``augment``, its augmented lips and mixture.  Before that the
@@ -571,3 +592,98 @@ class MultimodalTrainer:
             res.append([word_segments(self.tokenizer, txt_h[i, :max(0, int(tl_h[i]))], spans[i], tok[i], frame_rate)
                         for i in range(txt_h.shape[0])])
         return tuple(res)
+
+    # ---- transcription of unlabeled clips: text, word times and confidences, decoded and timed on the device ----
+    def transcribe(self, batch, nbest: int = 1, frame_rate: float = 25.0):
+        """Both speakers' transcripts of a batch that needs no ``text*`` and no ``mask*`` keys (forward_log_probs), in eval mode, with the
+        averaged weights under ``eval_ema``, decoded as evaluate() decodes (all T frames; ``eval_beam_width``, ``eval_lm``, ``eval_bias``).
+        Returns (results1, results2): per utterance a dict with ``text``, ``ids``, ``confidence`` (the utterance's: ``conf_aggregation`` of
+        its tokens' confidences), ``words`` (``align.word_segments`` with ``confidence``: word, start, end, score, confidence) and, with a
+        beam, ``nbest``: up to ``nbest`` (text, score) pairs in descending order.  Beam width 0: one confidence.greedy_timed call per
+        speaker.  Otherwise nbest_on_device, forced_align on the best hypothesis (T <= 408: its lattice is sized for T labels), then the
+        frame and span passes of confidence.py.  Nothing travels to the host before the end; then ONE transfer per speaker.  Every
+        module's train / eval mode is restored; a timed-out persistent BiLSTM launch raises here as it does from evaluate()."""
+        nbest, W = int(nbest), self.eval_beam_width
+        if not 1 <= nbest <= max(W, 1):
+            raise ValueError(f"transcribe: need 1 <= nbest <= max(eval_beam_width, 1), got nbest={nbest} with eval_beam_width={W}")
+        with self._inference():
+            if torch.device(self.device).type != "cuda":
+                raise RuntimeError("MultimodalTrainer.transcribe: the model runs on the GPU; there is no CPU fallback")
+            mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+            modes = [(sm, sm.training) for m in mods for sm in m.modules()]
+            for m in mods:
+                m.eval()
+            try:
+                out = self.forward_log_probs(batch)
+            finally:
+                for sm, was in modes:
+                    sm.training = was
+            self.fusion_module.stage_flag_check()
+            B, T, _ = out["log_probs1"].shape
+            packed = [self._transcribe_device(out["log_probs" + spk].float(), nbest) for spk in ("1", "2")]
+            host = [p.cpu() for p in packed]                       # the only transfers: one int32 block per speaker
+            self.fusion_module.drain_flag_check()                  # raises if a persistent BiLSTM launch timed out
+        return tuple(self._transcribe_host(h, B, T, nbest, frame_rate) for h in host)
+
+    def _transcribe_device(self, lp, nbest):
+        """One speaker's log-probs [B, T, V] -> flat int32 block on the device: [B][T + 1][5] = per token (id, first frame, end frame, bits of
+        its confidence, bits of its path score), the last row (number of tokens, bits of the utterance confidence, 0, 0, 0); with a beam then
+        [B][nbest][T + 2] = per hypothesis its ids, its length and the bits of its score."""
+        from ..beam_search import nbest_on_device
+        from ..confidence import frame_confidence, greedy_timed, span_confidence, utterance_confidence
+        blank, (B, T, _) = self.tokenizer.blank_id, lp.shape
+        method, alpha, agg = self.conf_method, self.conf_alpha, self.conf_aggregation
+        i32 = lambda x: x.contiguous().view(torch.int32)       # noqa: E731
+        if self.eval_beam_width == 0:
+            g = greedy_timed(lp, blank, None, method, alpha, agg)
+            ids, n, spans, tc, ts, extra = g.ids, g.lengths, g.spans, g.token_conf, self._greedy_token_scores(lp, g), []
+        else:
+            kw = {}
+            if self.eval_lm is not None:
+                kw.update(lm=self.eval_lm, lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
+            if self.eval_bias is not None:
+                kw.update(bias=self.eval_bias, bias_weight=self.eval_bias_weight)
+            hyp, hl, hs = nbest_on_device(lp, self.eval_beam_width, blank, nbest=nbest, **kw)[:3]
+            ids, n = hyp[:, 0], hl[:, 0].clamp_min(0)
+            al = forced_align(lp, ids, None, n, blank=blank)
+            tc = span_confidence(frame_confidence(lp, None, method, alpha), al.spans, None, agg)
+            spans, ts, extra = al.spans, al.token_scores, [torch.cat([hyp, hl[..., None], i32(hs)[..., None]], 2).reshape(-1)]
+        utt = utterance_confidence(tc, n, agg)
+        tail = torch.zeros((B, 1, 5), dtype=torch.int32, device=lp.device)
+        tail[:, 0, 0], tail[:, 0, 1] = n, i32(utt)
+        main = torch.cat([ids[..., None], spans, i32(tc)[..., None], i32(ts)[..., None]], 2)
+        return torch.cat([torch.cat([main, tail], 1).reshape(-1)] + extra)
+
+    @staticmethod
+    def _greedy_token_scores(lp, g):
+        """float32 [B, T]: the sum of lp[t][id_j] over the run of greedy token j (forced_align's token score), 0 padded, from T gathered
+        elements per utterance: the label of each frame from the runs, the path's emissions, their float64 running sum, its differences."""
+        B, T, _ = lp.shape
+        t = torch.arange(T, device=lp.device).expand(B, T).contiguous()
+        first, end = g.spans[..., 0].long(), g.spans[..., 1].long()
+        j = torch.searchsorted(torch.where(first < 0, T, first), t, right=True) - 1       # the last run that starts at or before frame t
+        jc = j.clamp_min(0)
+        inside = (j >= 0) & (t < end.gather(1, jc))
+        label = g.ids.long().gather(1, jc).clamp_min(0)
+        em = torch.where(inside, lp.gather(2, label[..., None])[..., 0], 0.0).double()
+        cs = F.pad(em.cumsum(1), (1, 0))
+        return (cs.gather(1, end.clamp_min(0)) - cs.gather(1, first.clamp_min(0))).float()
+
+    def _transcribe_host(self, flat, B, T, nbest, frame_rate):
+        f32 = lambda x: x.contiguous().view(torch.float32)     # noqa: E731
+        main = flat[:B * (T + 1) * 5].view(B, T + 1, 5)
+        hyps = flat[B * (T + 1) * 5:].view(B, nbest, T + 2) if self.eval_beam_width > 0 else None
+        tc, ts, utt = f32(main[:, :T, 3]), f32(main[:, :T, 4]), f32(main[:, T, 1]).tolist()
+        res = []
+        for i in range(B):
+            n = int(main[i, T, 0])
+            ids = main[i, :n, 0].tolist()
+            r = {"text": fast_decode(ids, self.tokenizer), "ids": ids, "confidence": utt[i],
+                 "words": word_segments(self.tokenizer, ids, main[i, :T, 1:3], ts[i], frame_rate, token_conf=tc[i],
+                                        aggregation=self.conf_aggregation)}
+            if hyps is not None:
+                sc = f32(hyps[i, :, T + 1]).tolist()
+                r["nbest"] = [(fast_decode(hyps[i, k, :int(hyps[i, k, T])].tolist(), self.tokenizer), sc[k])
+                              for k in range(nbest) if int(hyps[i, k, T]) >= 0]
+            res.append(r)
+        return res

@@ -766,3 +766,116 @@ def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths,
                                  ptr(spans) if Lmax else None, ptr(tok) if Lmax else None, ptr(score), ptr(ws), ws.numel() * 4, stream()),
             "av_ctc_align")
     return states, spans, tok, score
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# CTC confidences on the device (csrc/ctc_confidence.hip; the laws and the host path: confidence.py).  Lengths and spans stay on the
+# device, nothing in a call synchronises.
+# ---------------------------------------------------------------------------------------------------------------
+def _conf_codes(who: str, method=None, alpha=None, aggregation=None):
+    m = a = None
+    if method is not None:
+        if method not in L.CONF_METHODS:
+            raise ValueError(f"{who}: method must be one of {sorted(L.CONF_METHODS)}, got {method!r}")
+        m, alpha = L.CONF_METHODS[method], float(alpha)
+        if method == "tsallis":
+            if not 0.0 < alpha < float("inf"):                        # NaN fails both comparisons
+                raise ValueError(f"{who}: the tsallis alpha must be finite and > 0, got {alpha}")
+            if abs(alpha - 1.0) < 1.0 / 64.0:
+                raise ValueError(f"{who}: tsallis alpha {alpha} is within 1/64 of 1, where the law loses its digits: use method='entropy', "
+                                 "its alpha -> 1 limit")
+    if aggregation is not None:
+        if aggregation not in L.CONF_AGGREGATIONS:
+            raise ValueError(f"{who}: aggregation must be one of {sorted(L.CONF_AGGREGATIONS)}, got {aggregation!r}")
+        a = L.CONF_AGGREGATIONS[aggregation]
+    return m, alpha, a
+
+
+def _conf_rows(who: str, log_probs, batch_first: bool):
+    """The validated [B, T, V] / [T, B, V] block of a confidence call -> (view with contiguous rows, B, T, V, stride_b, stride_t)."""
+    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
+        raise RuntimeError(f"{who} (HIP): log_probs must be on the GPU; there is no CPU fallback (confidence.py runs host tensors)")
+    if log_probs.dim() != 3:
+        raise ValueError(f"{who}: log_probs must be [B, T, V] (or [T, B, V] with batch_first=False), got shape {tuple(log_probs.shape)}")
+    if log_probs.dtype != torch.float32:
+        raise TypeError(f"{who}: log_probs must be float32, got {log_probs.dtype}")
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    if batch_first:
+        (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
+    else:
+        (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+    if V < 2 or not 1 <= T <= 4096:
+        raise ValueError(f"{who}: need V >= 2 and 1 <= T <= 4096, got T={T} V={V}")
+    return lp, B, T, V, sb, st
+
+
+def _conf_lengths(who: str, t, B: int, device) -> Optional[Tensor]:
+    if t is None:
+        return None
+    if not isinstance(t, Tensor):
+        t = torch.as_tensor(t, dtype=torch.long)
+    if t.dim() != 1 or t.numel() != B:
+        raise ValueError(f"{who}: lengths must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError(f"{who}: lengths must be an integer tensor, got {t.dtype}")
+    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()
+
+
+def ctc_frame_conf(log_probs: Tensor, lengths=None, method: str = "tsallis", alpha: float = 0.33, batch_first: bool = True) -> Tensor:
+    """av_ctc_frame_conf: ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]; any view with a contiguous last dimension is
+    taken without a copy), ``lengths`` [B] on either side or None -> confidence fp32 [B, T] on the device, 0 for t >= T_b."""
+    m, alpha, _ = _conf_codes("ctc_frame_conf", method, alpha)
+    lp, B, T, V, sb, st = _conf_rows("ctc_frame_conf", log_probs, batch_first)
+    ln = _conf_lengths("ctc_frame_conf", lengths, B, lp.device)
+    conf = torch.empty((B, T), dtype=torch.float32, device=lp.device)
+    L.check(L.lib().av_ctc_frame_conf(ptr(lp), sb, st, ptr(ln), B, T, V, m, alpha, ptr(conf), stream()), "av_ctc_frame_conf")
+    return conf
+
+
+def ctc_span_conf(frame_conf: Tensor, spans: Tensor, lengths=None, aggregation: str = "min") -> Tensor:
+    """av_ctc_span_conf: ``frame_conf`` fp32 [B, T] on the GPU, ``spans`` integer [B, L, 2] (first frame, end exclusive) and ``lengths`` [B]
+    on either side -> fp32 [B, L] on the device."""
+    _, _, a = _conf_codes("ctc_span_conf", aggregation=aggregation)
+    if not isinstance(frame_conf, Tensor) or not frame_conf.is_cuda:
+        raise RuntimeError("ctc_span_conf (HIP): frame_conf must be on the GPU; there is no CPU fallback (confidence.py runs host tensors)")
+    if frame_conf.dim() != 2 or frame_conf.dtype != torch.float32:
+        raise TypeError(f"ctc_span_conf: frame_conf must be float32 [B, T], got {frame_conf.dtype} {tuple(frame_conf.shape)}")
+    B, T = frame_conf.shape
+    if not isinstance(spans, Tensor) or spans.dim() != 3 or spans.shape[0] != B or spans.shape[2] != 2:
+        raise ValueError(f"ctc_span_conf: spans must be [B={B}, L, 2], got "
+                         f"{tuple(spans.shape) if isinstance(spans, Tensor) else type(spans).__name__}")
+    if spans.dtype.is_floating_point or spans.dtype == torch.bool:
+        raise TypeError(f"ctc_span_conf: spans must be an integer tensor, got {spans.dtype}")
+    if not 1 <= T <= 4096:
+        raise ValueError(f"ctc_span_conf: need 1 <= T <= 4096, got T={T}")
+    dev = frame_conf.device
+    Ls = spans.shape[1]
+    cf = frame_conf.detach().contiguous()
+    sp = spans.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+    ln = _conf_lengths("ctc_span_conf", lengths, B, dev)
+    out = torch.empty((B, Ls), dtype=torch.float32, device=dev)
+    L.check(L.lib().av_ctc_span_conf(ptr(cf), ptr(sp), ptr(ln), B, T, Ls, a, ptr(out), stream()), "av_ctc_span_conf")
+    return out
+
+
+def ctc_greedy_timed(log_probs: Tensor, blank: int, lengths=None, method: str = "tsallis", alpha: float = 0.33, aggregation: str = "min",
+                     batch_first: bool = True):
+    """av_ctc_greedy_timed: one read of ``log_probs`` (as for ``ctc_frame_conf``) -> (ids int32 [B, T] padded with -1, lengths int32 [B],
+    spans int32 [B, T, 2] padded with -1, token_conf fp32 [B, T], frame_conf fp32 [B, T]) on the device."""
+    m, alpha, a = _conf_codes("ctc_greedy_timed", method, alpha, aggregation)
+    lp, B, T, V, sb, st = _conf_rows("ctc_greedy_timed", log_probs, batch_first)
+    blank = int(blank)
+    if not 0 <= blank < V:
+        raise ValueError(f"ctc_greedy_timed: blank {blank} outside [0, {V})")
+    dev = lp.device
+    ln = _conf_lengths("ctc_greedy_timed", lengths, B, dev)
+    ids = torch.empty((B, T), dtype=torch.int32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, T, 2), dtype=torch.int32, device=dev)
+    tok = torch.empty((B, T), dtype=torch.float32, device=dev)
+    conf = torch.empty((B, T), dtype=torch.float32, device=dev)
+    L.check(L.lib().av_ctc_greedy_timed(ptr(lp), sb, st, ptr(ln), B, T, V, blank, m, alpha, a, ptr(ids), ptr(cnt), ptr(spans), ptr(tok),
+                                        ptr(conf), stream()), "av_ctc_greedy_timed")
+    return ids, cnt, spans, tok, conf
