@@ -558,6 +558,28 @@ int av_adam_multi_ema(const void* ptrs, const long long* sizes, const float* hyp
                       const void* ema_only_ptrs, const long long* ema_only_sizes, const int* ema_only_chunk_tensor,
                       const long long* ema_only_chunk_start, int n_ema_only_chunks, float ema_decay, int ema_warmup, float* ema_state,
                       void* stream);
+/* av_adam_multi_ema with decoupled weight decay (AdamW) and a choice of schedule (csrc/optim.hip; optim.AvAdam(weight_decay=...,
+ * lr_schedule=...)).  The arguments of av_adam_multi_ema, and:
+ * weight_decay: [n_tensors] device floats lambda_t >= 0, 4-byte aligned, or NULL for none.  In a step that is not skipped tensor t is
+ *   multiplied by f_t = 1 - lr_t * m_k * lambda_t before its Adam update - torch.optim.AdamW's param.mul_(1 - lr * weight_decay) - with
+ *   lr_t = hyper[t][0] and m_k this step's learning-rate multiplier from clip_state (1 without a schedule).  f_t is computed once per
+ *   workgroup in double and stored as a float; p * f_t is rounded on its own, never contracted into the update.  The gradient and the
+ *   moments do not see the decay; shadow and EMA are written from the decayed, updated value.  A skipped step decays nothing, nor does a
+ *   warmup step at multiplier 0; a tensor that is not in the launch (no gradient) is not decayed; the clip coefficient scales the
+ *   gradient only.
+ * lr_schedule: 0 = the linear law of av_adam_multi_ex; 1 = cosine: k / warmup_steps while k < warmup_steps, then
+ *   max(0, 0.5 * (1 + cos(pi * (k - warmup_steps) / (total_steps - warmup_steps)))) - HF get_cosine_schedule_with_warmup with num_cycles = 0.5
+ *   - and 0 for k >= total_steps (HF's lambda rises again there), in double by the thread that computes the linear law.  Cosine needs
+ *   total_steps > warmup_steps and therefore clip_state.
+ * A misaligned table, an lr_schedule outside {0, 1}, cosine without total_steps or without clip_state are error statuses.  With
+ * weight_decay == NULL and lr_schedule == 0 this is av_adam_multi_ema: the same kernels are launched.  No host synchronisation. */
+int av_adam_multi_wd(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor, const long long* chunk_start,
+                     int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors, float grad_scale,
+                     float* scaler_state, float growth, float backoff, int growth_interval, float max_norm, int warmup_steps,
+                     int total_steps, void* workspace, long long workspace_bytes, float* clip_state, const void* ema_ptrs,
+                     const void* ema_only_ptrs, const long long* ema_only_sizes, const int* ema_only_chunk_tensor,
+                     const long long* ema_only_chunk_start, int n_ema_only_chunks, float ema_decay, int ema_warmup, float* ema_state,
+                     const float* weight_decay, int lr_schedule, void* stream);
 /* one multi-tensor launch that exchanges parameters and their averages: ptrs [n_tensors][3] device pointers {param, ema, shadow}, sizes
  * [n_tensors], chunk tables as av_adam_multi.  param and ema (fp32) change places element by element, without a temporary copy; where
  * shadow != 0 the new parameter's 16-bit image (bf16 in libavhip.so, half in libavhip_f16.so) is written there, as the Adam kernel does.

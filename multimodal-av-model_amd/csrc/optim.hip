@@ -1,7 +1,8 @@
 // The optimizer: fused Adam step (torch.optim.Adam defaults, model/trainer.py:34-39) with optional gradient scaling, and opt-in global-norm
 // gradient clipping and learning-rate schedule decided on the device (av_adam_multi_ex), an opt-in exponential moving average of the
-// weights kept by the same launch (av_adam_multi_ema) and the in-place exchange of weights and averages (av_param_swap_multi).
-// The three av_adam_multi* entry points fill one AdamLaunch record; adam_check validates it and adam_launch is the launch sequence.
+// weights kept by the same launch (av_adam_multi_ema), opt-in decoupled weight decay (AdamW) and a cosine schedule (av_adam_multi_wd) and
+// the in-place exchange of weights and averages (av_param_swap_multi).
+// The four av_adam_multi* entry points fill one AdamLaunch record; adam_check validates it and adam_launch is the launch sequence.
 #include "av_common.h"
 
 namespace {
@@ -131,9 +132,18 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const unsigned lo
 }
 
 // HF get_linear_schedule_with_warmup under LambdaLR: step k (0-based, steps actually taken) runs at k / warmup below warmup, then at
-// max(0, (total - k) / (total - warmup)); total == 0: constant 1 after the warmup.  optim.lr_multiplier is the same law on the host.
-__device__ __forceinline__ float lr_multiplier(int k, int warmup, int total) {
+// max(0, (total - k) / (total - warmup)); total == 0: constant 1 after the warmup.  schedule == LR_COSINE (av_adam_multi_wd; total > warmup):
+// after the same warmup max(0, 0.5 * (1 + cos(pi * x))), x = (k - warmup) / (total - warmup) - HF get_cosine_schedule_with_warmup with
+// num_cycles = 0.5 - and 0 from k = total on (HF's lambda rises again there).  optim.lr_multiplier is the same law on the host.
+enum { LR_LINEAR = 0, LR_COSINE = 1 };
+__device__ __forceinline__ float lr_multiplier(int k, int warmup, int total, int schedule) {
     if (k < warmup) return (float)((double)k / (double)warmup);
+    if (schedule == LR_COSINE) {
+        if (k >= total) return 0.f;
+        const double x = (double)(k - warmup) / (double)(total - warmup);
+        const double m = 0.5 * (1.0 + cos(3.14159265358979323846 * x));
+        return (float)(m > 0.0 ? m : 0.0);
+    }
     if (total == 0) return 1.f;
     const double m = (double)(total - k) / (double)(total - warmup);
     return (float)(m > 0.0 ? m : 0.0);
@@ -142,7 +152,8 @@ __device__ __forceinline__ float lr_multiplier(int k, int warmup, int total) {
 // one workgroup: the chunk partials summed in a fixed order -> norm, clip coefficient, found_inf (with clipping this pass replaces
 // grad_check_multi_kernel), and this step's learning-rate multiplier.  partial == NULL: clipping is off (schedule only).
 __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ partial, int n_chunks, float gscale, float max_norm,
-                                                            int warmup, int total, float* __restrict__ gs, float* __restrict__ cs) {
+                                                            int warmup, int total, float* __restrict__ gs, float* __restrict__ cs,
+                                                            int schedule) {
     __shared__ double red[4];
     double a = 0.0;
     if (partial)
@@ -161,7 +172,7 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
     }
     cs[CS_NORM] = norm;
     cs[CS_COEF] = coef;
-    cs[CS_LRM] = lr_multiplier(((const int*)cs)[CS_K], warmup, total);
+    cs[CS_LRM] = lr_multiplier(((const int*)cs)[CS_K], warmup, total, schedule);
 }
 
 // Exponential moving average of the weights (av_adam_multi_ema).  EMA state on the device, two 32-bit words:
@@ -201,13 +212,18 @@ __device__ __forceinline__ float ema_one(float ema, float p, float w, float omw)
 // the host knowing.  hyper[t] = {lr, beta1, beta2, eps}.  Bias corrections in double (1 - beta2^step loses half its digits in fp32).
 // EMA (av_adam_multi_ema): ema_ptrs[t] is the fp32 average of tensor t, moved towards the updated parameter while that is still in a
 // register; the EMA = false instantiation is the kernel of av_adam_multi / av_adam_multi_ex, statement for statement.
-template <bool EMA>
+// WD (av_adam_multi_wd): decoupled weight decay, torch.optim.AdamW's param.mul_(1 - lr * weight_decay) ahead of the update: wd[t] = lambda_t
+// and f_t = 1 - lr_t * lr_mult * lambda_t, once per workgroup in double, stored as a float; p * f_t is rounded on its own (__fmul_rn: never
+// contracted into the update), the gradient and the moments do not see it, shadow and EMA are written from the decayed, updated value.
+// The WD = false instantiations do not read wd and are the kernels they were.
+template <bool EMA, bool WD>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long long* __restrict__ ptrs, const long long* __restrict__ sizes,
                                                          const f32x4* __restrict__ hyper, const int* __restrict__ chunk_tensor,
                                                          const long long* __restrict__ chunk_start, int chunk_elems,
                                                          const int* __restrict__ steps, const int* __restrict__ step_slot, float gscale,
                                                          const float* __restrict__ gs, const float* __restrict__ cs,
-                                                         const unsigned long long* __restrict__ ema_ptrs, const float* __restrict__ es) {
+                                                         const unsigned long long* __restrict__ ema_ptrs, const float* __restrict__ es,
+                                                         const float* __restrict__ wd) {
     if (gs) {                                                    // loss scaling: skip on overflow, unscale
         if (gs[GS_INF] != 0.f) return;
         gscale *= gs[GS_INV];
@@ -237,6 +253,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
         ew = 1.f - es[ES_DECAY];
         eomw = 1.f - ew;
     }
+    float wf = 1.f;                                              // decay factor f_t
+    if constexpr (WD) wf = (float)(1.0 - (double)hp[0] * (double)lr_mult * (double)wd[t]);
     chunk_walk(sp, (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0) && ((uintptr_t)sh % 8 == 0),
         [&](long long e) {
             f32x4 pp = *(const f32x4*)(p + e), mm = *(const f32x4*)(m + e), vv = *(const f32x4*)(v + e);
@@ -247,6 +265,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float pk = pp[k], mk = mm[k], vk = vv[k];
+                if constexpr (WD) pk = __fmul_rn(pk, wf);
                 o[k] = (bf16_t)adam_one(pk, gg[k], mk, vk, b1, b2, eps, step_size, bc2_sqrt, gscale);
                 pp[k] = pk; mm[k] = mk; vv[k] = vk;
                 if constexpr (EMA) ee[k] = ema_one(ee[k], pk, ew, eomw);
@@ -257,6 +276,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
         },
         [&](long long i) {
             float pp = p[i], mm = m[i], vv = v[i];
+            if constexpr (WD) pp = __fmul_rn(pp, wf);
             const float r = adam_one(pp, g[i], mm, vv, b1, b2, eps, step_size, bc2_sqrt, gscale);
             p[i] = pp; m[i] = mm; v[i] = vv;
             if (sh) sh[i] = (bf16_t)r;
@@ -344,8 +364,9 @@ inline int ew_grid(long long n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-// One fused step, as the three av_adam_multi* entry points describe it.  An entry point fills the members it has arguments for; the rest
-// stay zero, which is "off" for each of them (max_norm 0: no clipping, both step counts 0: no schedule, decay 0: no EMA).
+// One fused step, as the four av_adam_multi* entry points describe it.  An entry point fills the members it has arguments for; the rest
+// stay zero, which is "off" for each of them (max_norm 0: no clipping, both step counts 0: no schedule, decay 0: no EMA, weight_decay NULL:
+// no decay, lr_schedule 0: the linear law).
 struct EmaArgs {
     const void* ema_ptrs;
     const void* only_ptrs;
@@ -366,6 +387,8 @@ struct AdamLaunch {
     float max_norm; int warmup_steps, total_steps; void* workspace; long long workspace_bytes; float* clip_state;
     // av_adam_multi_ema
     EmaArgs ema;
+    // av_adam_multi_wd
+    const float* weight_decay; int lr_schedule;
 
     bool clip() const { return max_norm > 0.f; }
     bool sched() const { return warmup_steps > 0 || total_steps > 0; }
@@ -382,6 +405,11 @@ int adam_check(const char* who, const AdamLaunch& a) {
     AV_CHECK(a.max_norm >= 0.f, "%s: max_norm must be >= 0 and not NaN (0 = no clipping)", who);
     AV_CHECK(a.warmup_steps >= 0 && a.total_steps >= 0 && (a.total_steps == 0 || a.total_steps > a.warmup_steps),
              "%s: bad schedule (warmup_steps %d, total_steps %d: total_steps must be 0 or above warmup_steps)", who, a.warmup_steps, a.total_steps);
+    AV_CHECK(a.lr_schedule == LR_LINEAR || a.lr_schedule == LR_COSINE, "%s: lr_schedule must be 0 (linear) or 1 (cosine), got %d", who,
+             a.lr_schedule);
+    AV_CHECK(a.lr_schedule != LR_COSINE || a.total_steps > 0, "%s: the cosine schedule needs total_steps > warmup_steps", who);
+    AV_CHECK(a.lr_schedule != LR_COSINE || a.clip_state, "%s: the cosine schedule needs the state block", who);
+    AV_CHECK(((uintptr_t)a.weight_decay % 4) == 0, "%s: the weight_decay table must be 4-byte aligned ([n_tensors] floats)", who);
     const bool clip = a.clip(), sched = a.sched();
     AV_CHECK(!(clip || sched) || a.clip_state, "%s: clipping or a schedule needs the state block", who);
     AV_CHECK(!(clip || sched) || ((uintptr_t)a.clip_state % 4) == 0, "%s: the state block must be 4-byte aligned", who);
@@ -400,7 +428,7 @@ int adam_check(const char* who, const AdamLaunch& a) {
 }
 
 // The launches of one step, in the order they run.  With clipping, schedule and EMA off only the lines of av_adam_multi are left:
-// [grad_check, with a scaler] -> adam_multi_kernel<false> -> adam_finish.
+// [grad_check, with a scaler] -> adam_multi_kernel<false, false> -> adam_finish.
 int adam_launch(const AdamLaunch& a, hipStream_t st) {
     const EmaArgs& ea = a.ema;
     const bool clip = a.clip(), sched = a.sched(), ema = a.averaging();
@@ -419,18 +447,19 @@ int adam_launch(const AdamLaunch& a, hipStream_t st) {
     // 2. norm, clip coefficient and learning-rate multiplier of this step
     if (adam && cs)
         hipLaunchKernelGGL(clip_finalize_kernel, one, wg, 0, st, clip ? (const double*)a.workspace : (const double*)nullptr, a.n_chunks,
-                           a.grad_scale, a.max_norm, a.warmup_steps, a.total_steps, gs, cs);
+                           a.grad_scale, a.max_norm, a.warmup_steps, a.total_steps, gs, cs, a.lr_schedule);
     // 3. EMA decay of this step
     if (ema_run) hipLaunchKernelGGL(ema_decay_kernel, one, one, 0, st, ea.decay, ea.warmup, ea.state);
-    // 4. Adam, with the EMA of the tensors it updates
-    if (adam && ema)
-        hipLaunchKernelGGL(adam_multi_kernel<true>, chunks, wg, 0, st, a.ptrs, a.sizes, (const f32x4*)a.hyper, a.chunk_tensor, a.chunk_start,
-                           a.chunk_elems, (const int*)a.steps, a.step_slot, a.grad_scale, (const float*)gs, (const float*)cs,
-                           (const unsigned long long*)ea.ema_ptrs, (const float*)ea.state);
-    else if (adam)
-        hipLaunchKernelGGL(adam_multi_kernel<false>, chunks, wg, 0, st, a.ptrs, a.sizes, (const f32x4*)a.hyper, a.chunk_tensor, a.chunk_start,
-                           a.chunk_elems, (const int*)a.steps, a.step_slot, a.grad_scale, (const float*)gs, (const float*)cs,
-                           (const unsigned long long*)nullptr, (const float*)nullptr);
+    // 4. Adam, with the decay and the EMA of the tensors it updates
+    if (adam) {
+        const bool wd = a.weight_decay != nullptr;
+        auto* const kernel = ema ? (wd ? adam_multi_kernel<true, true> : adam_multi_kernel<true, false>)
+                                 : (wd ? adam_multi_kernel<false, true> : adam_multi_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, chunks, wg, 0, st, a.ptrs, a.sizes, (const f32x4*)a.hyper, a.chunk_tensor, a.chunk_start, a.chunk_elems,
+                           (const int*)a.steps, a.step_slot, a.grad_scale, (const float*)gs, (const float*)cs,
+                           (const unsigned long long*)(ema ? ea.ema_ptrs : nullptr), (const float*)(ema ? ea.state : nullptr),
+                           a.weight_decay);
+    }
     // 5. EMA of the tensors without a gradient
     if (ema && ea.n_only_chunks > 0)
         hipLaunchKernelGGL(ema_only_multi_kernel, dim3(ea.n_only_chunks), wg, 0, st, (const unsigned long long*)ea.only_ptrs, ea.only_sizes,
@@ -495,6 +524,22 @@ extern "C" int av_adam_multi_ema(const void* ptrs, const long long* sizes, const
                           {ema_ptrs, ema_only_ptrs, ema_only_sizes, ema_only_chunk_tensor, ema_only_chunk_start, n_ema_only_chunks, ema_decay,
                            ema_warmup, ema_state}};
     return adam_step("av_adam_multi_ema", a, stream);
+}
+extern "C" int av_adam_multi_wd(const void* ptrs, const long long* sizes, const float* hyper, const int* chunk_tensor,
+                                const long long* chunk_start, int n_chunks, int chunk_elems, int* steps, const int* step_slot, int n_tensors,
+                                float grad_scale, float* scaler_state, float growth, float backoff, int growth_interval, float max_norm,
+                                int warmup_steps, int total_steps, void* workspace, long long workspace_bytes, float* clip_state,
+                                const void* ema_ptrs, const void* ema_only_ptrs, const long long* ema_only_sizes,
+                                const int* ema_only_chunk_tensor, const long long* ema_only_chunk_start, int n_ema_only_chunks,
+                                float ema_decay, int ema_warmup, float* ema_state, const float* weight_decay, int lr_schedule,
+                                void* stream) {
+    const AdamLaunch a = {(const unsigned long long*)ptrs, sizes, hyper, chunk_tensor, chunk_start, n_chunks, chunk_elems, steps, step_slot,
+                          n_tensors, grad_scale, scaler_state, growth, backoff, growth_interval,
+                          max_norm, warmup_steps, total_steps, workspace, workspace_bytes, clip_state,
+                          {ema_ptrs, ema_only_ptrs, ema_only_sizes, ema_only_chunk_tensor, ema_only_chunk_start, n_ema_only_chunks, ema_decay,
+                           ema_warmup, ema_state},
+                          weight_decay, lr_schedule};
+    return adam_step("av_adam_multi_wd", a, stream);
 }
 extern "C" int av_param_swap_multi(const void* ptrs, const long long* sizes, const int* chunk_tensor, const long long* chunk_start,
                                    int n_chunks, int chunk_elems, void* stream) {

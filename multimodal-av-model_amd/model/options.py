@@ -41,6 +41,11 @@ OPTIONS = {
     "max_grad_norm": ("AVAMD_CLIP_NORM", float, "0", float),
     "warmup_steps": ("AVAMD_WARMUP_STEPS", int, "0", int),
     "total_steps": ("AVAMD_TOTAL_STEPS", int, "0", int),
+    # decoupled weight decay (torch.optim.AdamW's law; the same value for all four groups, tensors with ndim <= 1 - biases, norm weights, PReLU
+    # slopes - not decayed) and the schedule after the warmup ("linear", or "cosine": optim.lr_multiplier(..., schedule="cosine"), needs
+    # total_steps), both inside the same fused step.  Data parallel: every rank computes the same bytes, nothing is communicated
+    "weight_decay": ("AVAMD_WEIGHT_DECAY", float, "0", float),
+    "lr_schedule": ("AVAMD_LR_SCHEDULE", str, "linear", str),
     # an exponential moving average of the trainable weights inside the same fused step (skipped with an overflowing step, moved for LayerDrop-ped
     # layers too); ema_warmup: optim.ema_decay's.  eval_ema: evaluate() and align() run on the averages (swapped in and back in place; BatchNorm
     # buffers are not averaged, AveragedModel's default).  Data parallel: every rank computes the same averages, nothing is communicated
@@ -84,3 +89,10 @@ def check_confidence(method: str, alpha: float, aggregation: str) -> None:
 def check_ema(eval_ema: bool, ema_decay: float) -> None:
     if eval_ema and not ema_decay > 0:
         raise ValueError("eval_ema needs ema_decay > 0: there is no averaged model to evaluate")
+
+
+def check_schedule(lr_schedule: str, total_steps: int) -> None:
+    if lr_schedule not in ("linear", "cosine"):
+        raise ValueError(f"lr_schedule must be 'linear' or 'cosine', got {lr_schedule!r}")
+    if lr_schedule == "cosine" and not total_steps > 0:
+        raise ValueError("lr_schedule='cosine' needs total_steps > 0: the cosine has to know where it ends")

@@ -71,7 +71,8 @@ class MultimodalTrainer:
                  mwer_beam: Optional[int] = None, mwer_level: str = "word", max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
                  ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None, conf_method: Optional[str] = None,
-                 conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None):
+                 conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None, weight_decay: Optional[float] = None,
+                 lr_schedule: Optional[str] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -109,6 +110,8 @@ class MultimodalTrainer:
                            + list(self.fusion_module.parameters()) + list(self.decoder1.parameters()))
         self.max_grad_norm, self.warmup_steps = opt("max_grad_norm", max_grad_norm), opt("warmup_steps", warmup_steps)
         self.total_steps = opt("total_steps", total_steps)
+        self.weight_decay, self.lr_schedule = opt("weight_decay", weight_decay), opt("lr_schedule", lr_schedule)
+        options.check_schedule(self.lr_schedule, self.total_steps)
         self.ema_decay, self.ema_warmup = opt("ema_decay", ema_decay), opt("ema_warmup", ema_warmup)
         self.eval_ema = opt("eval_ema", eval_ema)
         options.check_ema(self.eval_ema, self.ema_decay)
@@ -118,7 +121,7 @@ class MultimodalTrainer:
             {"params": list(self.fusion_module.parameters()), "lr": learning_rate},
             {"params": list(self.decoder1.parameters()), "lr": learning_rate},
         ], max_grad_norm=self.max_grad_norm, warmup_steps=self.warmup_steps, total_steps=self.total_steps, ema_decay=self.ema_decay,
-            ema_warmup=self.ema_warmup)                                                     # ValueError on bad values
+            ema_warmup=self.ema_warmup, weight_decay=self.weight_decay, lr_schedule=self.lr_schedule)    # ValueError on bad values
         # model/trainer.py:40 (GradScaler); off by default: bf16 operands need no loss scaling.  On = the reference's overflow-skip /
         # growth / backoff law, evaluated on the device
         self.scaler = AvGradScaler(device=device, enabled=loss_scaling)

@@ -4,10 +4,12 @@ checkpoint dict (main.py:47-55) stays loadable.  ``grad_scale`` folds the data-p
 un-scale) into the step so that no extra pass over the gradients is needed.  Opt-in (``max_grad_norm`` / ``warmup_steps`` /
 ``total_steps``): global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, decided on the device inside
 the same fused step.  Opt-in (``ema_decay``): an exponential moving average of the weights kept by that step, and
-``swap_averaged`` / ``averaged`` to evaluate and save with it."""
+``swap_averaged`` / ``averaged`` to evaluate and save with it.  Opt-in (``weight_decay`` / ``lr_schedule="cosine"``):
+decoupled weight decay - torch.optim.AdamW's law - and a warmup + cosine schedule, inside the same step."""
 from __future__ import annotations
 
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -65,14 +67,24 @@ class AvGradScaler:
         self.state[GS_STEP] = float(sd.get("_steps_taken", 0))
 
 
-def lr_multiplier(k: int, warmup_steps: int = 0, total_steps: int = 0) -> float:
+LR_SCHEDULES = {"linear": 0, "cosine": 1}                          # lr_schedule of av_adam_multi_wd
+
+
+def lr_multiplier(k: int, warmup_steps: int = 0, total_steps: int = 0, schedule: str = "linear") -> float:
     """Learning-rate multiplier of optimizer step ``k`` (0-based, counting steps actually taken): HF get_linear_schedule_with_warmup under
     torch.optim.lr_scheduler.LambdaLR - k / warmup below the warmup, then max(0, (total - k) / (total - warmup)); ``total_steps == 0``:
-    constant 1 after the warmup; both 0: always 1.  The host form of the law the fused step evaluates on the device (tests, logging).
+    constant 1 after the warmup; both 0: always 1.  ``schedule="cosine"`` (needs total_steps > warmup_steps): after the same warmup
+    max(0, 0.5 * (1 + cos(pi * (k - warmup) / (total - warmup)))), HF get_cosine_schedule_with_warmup with num_cycles = 0.5, and 0 from
+    k = total on (HF's lambda rises again there).  The host form of the law the fused step evaluates on the device (tests, logging).
     With a warmup step 0 runs at multiplier 0, as in torch: moments and step counts advance, the parameters do not move."""
     k, warmup_steps, total_steps = int(k), int(warmup_steps), int(total_steps)
+    check_lr_schedule(schedule, warmup_steps, total_steps)
     if k < warmup_steps:
         return k / warmup_steps
+    if schedule == "cosine":
+        if k >= total_steps:
+            return 0.0
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((k - warmup_steps) / (total_steps - warmup_steps)))))
     if total_steps == 0:
         return 1.0
     return max(0.0, (total_steps - k) / (total_steps - warmup_steps))
@@ -88,6 +100,23 @@ def check_clip_schedule(max_grad_norm, warmup_steps, total_steps):
     if total_steps != 0 and total_steps <= warmup_steps:
         raise ValueError(f"total_steps must be 0 (no decay) or above warmup_steps, got total_steps={total_steps} warmup_steps={warmup_steps}")
     return max_grad_norm, warmup_steps, total_steps
+
+
+def check_lr_schedule(lr_schedule, warmup_steps, total_steps):
+    """The code of ``lr_schedule`` ("linear" 0, "cosine" 1); ValueError for another name, and for cosine without total_steps > warmup_steps."""
+    if lr_schedule not in LR_SCHEDULES:
+        raise ValueError(f"lr_schedule must be 'linear' or 'cosine', got {lr_schedule!r}")
+    if lr_schedule == "cosine" and not int(total_steps) > max(0, int(warmup_steps)):
+        raise ValueError(f"lr_schedule='cosine' needs total_steps above warmup_steps, got total_steps={total_steps} warmup_steps={warmup_steps}")
+    return LR_SCHEDULES[lr_schedule]
+
+
+def check_weight_decay(weight_decay):
+    """Validated weight_decay (finite, >= 0; 0 = none); ValueError otherwise."""
+    weight_decay = float(weight_decay)
+    if not 0.0 <= weight_decay < float("inf"):                  # NaN fails both comparisons
+        raise ValueError(f"weight_decay must be finite and >= 0 (0 = no decay), got {weight_decay}")
+    return weight_decay
 
 
 def ema_decay(k: int, decay: float, warmup: bool = False) -> float:
@@ -170,8 +199,9 @@ class _StateBlock:
 class _Plan:
     """Static part of one multi-tensor launch (cached per set of (parameter, hyper-parameters)): sizes, {lr, beta1, beta2, eps} per tensor,
     chunk table, step-table slots - and the pointer table of its last launch.  With an EMA also sizes and chunk table of the "EMA-only"
-    tensors (an average, no gradient in this pattern) and the EMA pointer table [n] + [n_only][2]."""
-    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptrs", "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema")
+    tensors (an average, no gradient in this pattern) and the EMA pointer table [n] + [n_only][2].  ``wd``: the weight decay of each tensor,
+    None when every one is 0."""
+    __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptrs", "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema", "wd")
 
 
 class AvAdam(torch.optim.Optimizer):
@@ -191,16 +221,26 @@ class AvAdam(torch.optim.Optimizer):
     scaling the device skips it with the step.  ``swap_averaged()`` / ``averaged()`` exchange parameters and averages in place, 16-bit
     shadows included.  Data parallel: every rank computes the same averages from the same bytes, nothing is communicated.
 
-    Every step is one call of ``av_adam_multi_ema`` with zeros and NULLs for what is off: by that function's contract this is
-    ``av_adam_multi_ex`` without an EMA and ``av_adam_multi`` with clipping and schedule off as well - the same kernels are launched."""
+    ``weight_decay`` (a per-group key, as in torch.optim.AdamW; a group without it - a state dict from before - runs at the constructor's
+    value) multiplies a tensor by ``1 - lr * lr_multiplier(k) * weight_decay`` ahead of its Adam update, inside the same launch: AdamW's
+    decoupled law, so a skipped step, a warmup step at multiplier 0 and a tensor without a gradient decay nothing.  Tensors with
+    ``ndim <= 1`` (biases, LayerNorm / BatchNorm weights, PReLU slopes) are not decayed unless ``decay_1d`` is set: the usual rule, without
+    splitting groups.  ``lr_schedule="cosine"`` replaces the linear decay after the warmup by ``lr_multiplier(..., schedule="cosine")`` and
+    needs ``total_steps``.
+
+    Every step is one call of ``av_adam_multi_wd`` with zeros and NULLs for what is off: by that function's contract this is
+    ``av_adam_multi_ema`` without decay and cosine, ``av_adam_multi_ex`` without an EMA and ``av_adam_multi`` with clipping and schedule off as
+    well - the same kernels are launched."""
 
     SCHEDULE_KEY = "av_schedule_step"     # state_dict entry of the schedule step; torch.optim.Adam.load_state_dict ignores it
     EMA_KEY = "av_ema_step"               # ... of the count of EMA updates
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, warmup_steps=0, total_steps=0, ema_decay=0.0,
-                 ema_warmup=False):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+                 ema_warmup=False, weight_decay=0.0, decay_1d=False, lr_schedule="linear"):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=check_weight_decay(weight_decay)))
         self.max_grad_norm, self.warmup_steps, self.total_steps = check_clip_schedule(max_grad_norm, warmup_steps, total_steps)
+        self.lr_schedule, self.decay_1d = lr_schedule, bool(decay_1d)
+        self._lr_schedule = check_lr_schedule(lr_schedule, self.warmup_steps, self.total_steps)
         self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
         self._ema_state = _StateBlock(2, ES_K)     # {decay of the last update, count of updates}
         self._swapped = False         # swap_averaged(): the parameters currently hold the averages
@@ -213,7 +253,7 @@ class AvAdam(torch.optim.Optimizer):
         self._steps_dev = None
         self._steps_seeded = False
         self._keep = None             # the last step's gradients, alive until the next step (stream-ordered use)
-        self.fused_launches = 0       # diagnostics / tests: every step is one av_adam_multi_ema call
+        self.fused_launches = 0       # diagnostics / tests: every step is one av_adam_multi_wd call
 
     CHUNK = 65536
 
@@ -366,15 +406,18 @@ class AvAdam(torch.optim.Optimizer):
         if getattr(self, "_steps_dev", None) is not None:
             self.sync_steps()                                       # the device table is rebuilt below: seed it from CURRENT counts
         super().add_param_group(param_group)
+        check_weight_decay(self.param_groups[-1]["weight_decay"])
         self._slot = None
         self._steps_dev = None
         self._steps_seeded = False
         self._plans = {}
         self._clip_ws = None                                        # sized by the chunks of all parameters
 
-    def _plan(self, plist, dev, ema_only=None) -> _Plan:
+    def _plan(self, plist, dev, ema_only=None, decays=None) -> _Plan:
         slots = self._slots()
         key = tuple((p.data_ptr(), p.numel(), hp, slots[id(p)]) for p, hp, _ in plist)
+        if decays is not None:                                      # some tensor is decayed: the values are part of the plan
+            key = (key, "wd", tuple(decays))
         if ema_only is not None:                                    # with an EMA the tensors WITHOUT a gradient are part of the pattern
             key = (key, tuple((p.data_ptr(), p.numel()) for p in ema_only))
         pl = self._plans.get(key)
@@ -391,6 +434,7 @@ class AvAdam(torch.optim.Optimizer):
             pl.eo_sizes, pl.eo_ct, pl.eo_cs, pl.eo_nch = (_size_tables([p.numel() for p in ema_only], self.CHUNK, dev) if pl.eo_n
                                                           else (None, None, None, 0))
             pl.ema = _PtrTable(pl.n + 2 * pl.eo_n, dev) if ema_only is not None else None
+            pl.wd = ops.h2d_async(np.asarray(decays, dtype=np.float32), dev) if decays is not None else None
             self._plans[key] = pl
         return pl
 
@@ -409,13 +453,15 @@ class AvAdam(torch.optim.Optimizer):
                     st["step"] = int(host[slots[id(p)]])
 
     def _collect(self):
-        """(plist, ema_only): (parameter, {lr, beta1, beta2, eps}, state) of every parameter with a gradient, its state created at its
-        first step; with an EMA, the parameters that have an average and no gradient in this step (still moved towards p), else None."""
-        plist = []
+        """(plist, ema_only, decays): (parameter, {lr, beta1, beta2, eps}, state) of every parameter with a gradient, its state created at
+        its first step; with an EMA, the parameters that have an average and no gradient in this step (still moved towards p), else None;
+        the weight decay of each tensor of plist, or None when none of them is decayed."""
+        plist, decays = [], []
         ema_only = [] if self.averaging else None
         for group in self.param_groups:
             b1, b2 = group["betas"]
             hp = (float(group["lr"]), float(b1), float(b2), float(group["eps"]))
+            wd = check_weight_decay(group.get("weight_decay", self.defaults["weight_decay"]))
             for p in group["params"]:
                 if p.grad is None:
                     if ema_only is not None and "ema" in self.state.get(p, ()):
@@ -431,7 +477,8 @@ class AvAdam(torch.optim.Optimizer):
                 if ema_only is not None and "ema" not in state:
                     state["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
                 plist.append((p, hp, state))
-        return plist, ema_only
+                decays.append(wd if self.decay_1d or p.ndim > 1 else 0.0)
+        return plist, ema_only, decays if any(decays) else None
 
     def _bind(self, pl, plist, ema_only, grads, shadows) -> None:
         """This step's pointers into the plan's tables: {param, grad, exp_avg, exp_avg_sq, shadow} per tensor and, with an EMA, the
@@ -456,11 +503,12 @@ class AvAdam(torch.optim.Optimizer):
             only = pl.ema.dev.data_ptr() + 8 * pl.n if pl.eo_n else None
             ema = (ops.ptr(pl.ema.dev), only, ops.ptr(pl.eo_sizes), ops.ptr(pl.eo_ct), ops.ptr(pl.eo_cs), pl.eo_nch, self.ema_decay,
                    int(self.ema_warmup), ops.ptr(self._ema_state.on(dev)))
-        L.check(L.lib().av_adam_multi_ema(ops.ptr(pl.ptrs.dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
-                                          self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), *scale,
-                                          self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
-                                          ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), *ema, ops.stream()),
-                "av_adam_multi_ema")
+        L.check(L.lib().av_adam_multi_wd(ops.ptr(pl.ptrs.dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
+                                         self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), *scale,
+                                         self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
+                                         ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), *ema, ops.ptr(pl.wd),
+                                         self._lr_schedule, ops.stream()),
+                "av_adam_multi_wd")
         self.fused_launches += 1
 
     def step(self, closure=None, scaler: "AvGradScaler" = None):
@@ -468,13 +516,13 @@ class AvAdam(torch.optim.Optimizer):
         if self._swapped:
             raise RuntimeError("AvAdam.step: the parameters hold the averaged weights (swap_averaged); swap back before stepping")
         loss = closure() if closure is not None else None
-        plist, ema_only = self._collect()
+        plist, ema_only, decays = self._collect()
         if not plist:
             return loss
         params = [p for p, _, _ in plist]
         dev = params[0].device
         steps = self._step_table(dev)                               # BEFORE the host counts move: a fresh table is seeded from them
-        pl = self._plan(plist, dev, ema_only)
+        pl = self._plan(plist, dev, ema_only, decays)
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
         shadows = shadow.lookup_many(params)                        # bf16 compute copies (perf path), written by the kernel
         self._bind(pl, plist, ema_only, grads, shadows)

@@ -4,7 +4,7 @@ plain step and against the only form available before:
   (a) the plain step                                      (AvAdam, everything off),
   (b) the step with clipping and schedule                 (AvAdam(max_grad_norm=1.0, warmup_steps=10, total_steps=1000)),
   (c) torch.nn.utils.clip_grad_norm_ followed by (a).
-Every side is one av_adam_multi_ema call, with zeros for what is off.  Alternating triples in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
+Every side is one av_adam_multi_wd call, with zeros for what is off.  Alternating triples in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
 profiles/adam_clip_timing.txt; records, gates nothing.
 
     python tools/clip_timing.py [--out profiles/adam_clip_timing.txt] [--rounds 30]

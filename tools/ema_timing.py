@@ -5,7 +5,7 @@ available before:
   (b) the step with the EMA                               (AvAdam(ema_decay=0.999): the average moves inside the Adam launch),
   (c) (a) followed by torch._foreach_lerp_ over cloned EMA tensors (what torch.optim.swa_utils.AveragedModel runs after the step; blind to
       skipped steps and to the 16-bit shadows).
-(a) and (b) are the same native call, av_adam_multi_ema, with and without a decay.  Also (d), av_param_swap_multi: one exchange of parameters and averages, as evaluate() with eval_ema pays twice per call.
+(a) and (b) are the same native call, av_adam_multi_wd, with and without an EMA decay.  Also (d), av_param_swap_multi: one exchange of parameters and averages, as evaluate() with eval_ema pays twice per call.
 Alternating rounds in steady state within one process, device events, median and range; bytes computed from the shapes.  Writes
 profiles/adam_ema_timing.txt; records, gates nothing.
 
