@@ -586,6 +586,16 @@ int av_adam_multi_wd(const void* ptrs, const long long* sizes, const float* hype
  * Calling it twice restores every bit. */
 int av_param_swap_multi(const void* ptrs, const long long* sizes, const int* chunk_tensor, const long long* chunk_start, int n_chunks,
                         int chunk_elems, void* stream);
+/* one multi-tensor launch that folds the gradients of a micro-batch into their accumulators (optim.AvAdam.accumulate): ptrs [n_tensors][2]
+ * device pointers {grad, acc}, both fp32; grad and acc of a tensor may not overlap.  mode [n_tensors] device ints: 0 = acc := grad, the
+ * tensor's first contribution of a cycle (no clearing pass, no read of acc, the gradient's own bits: autograd's first .grad is the gradient,
+ * not 0 + g); 1 = acc := acc + grad, one fp32 add per element.  sizes [n_tensors], chunk tables as av_adam_multi: one 256-thread workgroup
+ * per chunk, 16-byte accesses where both pointers are 16-byte aligned and the span starts on a multiple of 4, element by element otherwise.
+ * No LDS, no atomics: the same bits whatever the grid.  Non-finite values propagate by IEEE arithmetic; nothing is checked.  NULL tables,
+ * n_chunks < 0 or chunk_elems <= 0 are an error status ("av_grad_accum_multi: bad args"); n_chunks == 0 returns AV_OK without a launch.
+ * No host synchronisation. */
+int av_grad_accum_multi(const void* ptrs, const int* mode, const long long* sizes, const int* chunk_tensor, const long long* chunk_start,
+                        int n_chunks, int chunk_elems, void* stream);
 
 /* ---- legacy mel + GRU model (reference: "이전 버전/multimodal_ctc_korean.py":8-55, train loop
  * "이전 버전/train_ctc_korea.py":82-109).  Its convolutions (nn.Conv2d 3x3, :12,15) and all input / weight-gradient products run on

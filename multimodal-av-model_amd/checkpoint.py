@@ -12,7 +12,11 @@ KEYS = ("epoch", "visual_encoder", "audio_encoder", "fusion", "decoder1", "optim
 def checkpoint_dict(epoch: int, trainer, averaged: bool = False) -> dict:
     """``averaged``: the four module state_dicts hold the optimizer's averaged weights (AvAdam(ema_decay=...): taken under
     ``optimizer.averaged()`` and cloned; BatchNorm buffers and parameters without an average are the trained ones); the optimizer entry is
-    the one from before the swap, so the file resumes training as an ordinary checkpoint would.  Same layout either way."""
+    the one from before the swap, so the file resumes training as an ordinary checkpoint would.  Same layout either way.  An open gradient
+    accumulation cycle is not saved, and dropping it would make the resumed run differ from the uninterrupted one: it is refused."""
+    if getattr(trainer.optimizer, "accum_pending", 0) > 0:
+        raise ValueError(f"checkpoint_dict: {trainer.optimizer.accum_pending} accumulated micro-step(s) are waiting for their optimizer step; "
+                         "call trainer.flush_accumulated() first (or save at a cycle boundary)")
     sc = getattr(trainer, "scaler", None)
     if sc is not None and sc.enabled:
         trainer.optimizer.sync_steps(sc)             # steps actually taken (overflowing steps are skipped on the device)

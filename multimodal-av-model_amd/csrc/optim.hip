@@ -1,7 +1,7 @@
 // The optimizer: fused Adam step (torch.optim.Adam defaults, model/trainer.py:34-39) with optional gradient scaling, and opt-in global-norm
 // gradient clipping and learning-rate schedule decided on the device (av_adam_multi_ex), an opt-in exponential moving average of the
 // weights kept by the same launch (av_adam_multi_ema), opt-in decoupled weight decay (AdamW) and a cosine schedule (av_adam_multi_wd) and
-// the in-place exchange of weights and averages (av_param_swap_multi).
+// the in-place exchange of weights and averages (av_param_swap_multi), and the accumulation of micro-batch gradients (av_grad_accum_multi).
 // The four av_adam_multi* entry points fill one AdamLaunch record; adam_check validates it and adam_launch is the launch sequence.
 #include "av_common.h"
 
@@ -332,6 +332,30 @@ __global__ __launch_bounds__(256) void param_swap_multi_kernel(const unsigned lo
         });
 }
 
+// av_grad_accum_multi: ptrs[t] = {grad, acc}, both fp32, not overlapping.  mode[t] == 0: acc = grad, the tensor's first contribution of an
+// accumulation cycle - no clearing pass, no read of stale memory, and the bits of the gradient (a -0.0 stays -0.0, which 0 + g would not
+// keep): autograd's first .grad is the gradient itself.  mode[t] == 1: acc = acc + grad, one fp32 add per element: nothing to contract,
+// non-finite values propagate by IEEE arithmetic, no LDS, no atomics, every element written by one thread: the same bits whatever the grid.
+// The mode is uniform over a workgroup.  Bound by 12 B (add) or 8 B (copy) per element.  The quad loop is not unrolled: on the headline
+// configuration's 64.9 M elements chunk_walk<4> (30 VGPRs instead of 16) measured 0.159 / 0.101 ms for add / copy against 0.159 / 0.102 ms
+// without, 4.9 and 5.1 TB/s either way (tools/accum_timing.py, profiles/grad_accum_timing.txt): eight waves per SIMD keep enough loads in flight.
+__global__ __launch_bounds__(256) void grad_accum_multi_kernel(const unsigned long long* __restrict__ ptrs, const int* __restrict__ mode,
+                                                               const long long* __restrict__ sizes, const int* __restrict__ chunk_tensor,
+                                                               const long long* __restrict__ chunk_start, int chunk_elems) {
+    const ChunkSpan sp = chunk_span(sizes, chunk_tensor, chunk_start, chunk_elems);
+    const float* g = (const float*)ptrs[2 * sp.t + 0];
+    float* a = (float*)ptrs[2 * sp.t + 1];
+    const bool aligned = ((uintptr_t)g | (uintptr_t)a) % 16 == 0;
+    if (mode[sp.t] == 0)
+        chunk_walk(sp, aligned,
+            [&](long long e) { *(f32x4*)(a + e) = *(const f32x4*)(g + e); },
+            [&](long long i) { a[i] = g[i]; });
+    else
+        chunk_walk(sp, aligned,
+            [&](long long e) { *(f32x4*)(a + e) = *(const f32x4*)(a + e) + *(const f32x4*)(g + e); },
+            [&](long long i) { a[i] = a[i] + g[i]; });
+}
+
 // after the Adam launch (stream order): the tensors of that launch have taken one more step - unless the step was skipped for overflow.
 // With a scaler this launch also applies the GradScaler update law (one thread); sched_k (optional) is the schedule's step counter, ema_k
 // (optional) the count of EMA updates.
@@ -547,6 +571,15 @@ extern "C" int av_param_swap_multi(const void* ptrs, const long long* sizes, con
     if (n_chunks == 0) return AV_OK;
     hipLaunchKernelGGL(param_swap_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)ptrs, sizes,
                        chunk_tensor, chunk_start, chunk_elems);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+extern "C" int av_grad_accum_multi(const void* ptrs, const int* mode, const long long* sizes, const int* chunk_tensor,
+                                   const long long* chunk_start, int n_chunks, int chunk_elems, void* stream) {
+    AV_CHECK(ptrs && mode && sizes && chunk_tensor && chunk_start && n_chunks >= 0 && chunk_elems > 0, "av_grad_accum_multi: bad args");
+    if (n_chunks == 0) return AV_OK;
+    hipLaunchKernelGGL(grad_accum_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long*)ptrs, mode, sizes, chunk_tensor, chunk_start, chunk_elems);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -52,6 +52,10 @@ OPTIONS = {
     "ema_decay": ("AVAMD_EMA_DECAY", float, "0", float),
     "ema_warmup": ("AVAMD_EMA_WARMUP", _is1, "0", bool),
     "eval_ema": ("AVAMD_EVAL_EMA", _is1, "0", bool),
+    # gradient accumulation: every train_step is one micro-step whose gradients are summed on the device (optim.AvAdam.accumulate), and every
+    # accum_steps-th ends with ONE fused step on the mean - clipping, schedule, EMA, decay and loss scaling per optimizer step.  1: no accumulation.
+    # Data parallel: every micro-step all-reduces its buckets as a step does, so every rank accumulates the same bytes
+    "accum_steps": ("AVAMD_ACCUM_STEPS", int, "1", int),
     # transcribe()'s confidences (confidence.py): the frame measure ("tsallis", "entropy", "max_prob"), the Tsallis exponent, and how a token's
     # frames, a word's tokens and an utterance's tokens are aggregated ("min", "mean", "prod"); read by transcribe() alone
     "conf_method": ("AVAMD_CONF_METHOD", str, "tsallis", str),
@@ -89,6 +93,11 @@ def check_confidence(method: str, alpha: float, aggregation: str) -> None:
 def check_ema(eval_ema: bool, ema_decay: float) -> None:
     if eval_ema and not ema_decay > 0:
         raise ValueError("eval_ema needs ema_decay > 0: there is no averaged model to evaluate")
+
+
+def check_accum(accum_steps: int) -> None:
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps must be >= 1 (1 = no accumulation), got {accum_steps}")
 
 
 def check_schedule(lr_schedule: str, total_steps: int) -> None:

@@ -72,7 +72,7 @@ class MultimodalTrainer:
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
                  ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None, conf_method: Optional[str] = None,
                  conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None, weight_decay: Optional[float] = None,
-                 lr_schedule: Optional[str] = None):
+                 lr_schedule: Optional[str] = None, accum_steps: Optional[int] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -115,6 +115,8 @@ class MultimodalTrainer:
         self.ema_decay, self.ema_warmup = opt("ema_decay", ema_decay), opt("ema_warmup", ema_warmup)
         self.eval_ema = opt("eval_ema", eval_ema)
         options.check_ema(self.eval_ema, self.ema_decay)
+        self.accum_steps = opt("accum_steps", accum_steps)
+        options.check_accum(self.accum_steps)
         self.optimizer = AvAdam([
             {"params": list(self.visual_encoder.parameters()), "lr": learning_rate},
             {"params": list(self.audio_encoder.parameters()), "lr": 2e-5},
@@ -410,7 +412,9 @@ class MultimodalTrainer:
 
     def train_step(self, batch) -> Dict[str, torch.Tensor]:
         """zero_grad -> forward -> backward (-> bucketed all-reduce) -> Adam; no host sync.  With max_grad_norm > 0 the result also has
-        ``grad_norm``: the global gradient norm before clipping, a device scalar."""
+        ``grad_norm``: the global gradient norm before clipping, a device scalar.  With accum_steps > 1 every call is one micro-step: its
+        gradients go into the optimizer's accumulators, and the call that completes the cycle ends with the Adam step on their mean;
+        ``stepped`` (a bool) says which, and ``grad_norm`` is there only on those calls."""
         self.optimizer.zero_grad(set_to_none=True)
         self._head_arena.begin_step()
         begin = getattr(self.audio_encoder.model, "begin_grad_step", None)
@@ -430,11 +434,25 @@ class MultimodalTrainer:
                 self._reduce_head()
             self.reducer.wait()
             self._head_done = False
+        if self.accum_steps > 1:
+            self.optimizer.accumulate()                            # the arenas are free for the next backward (stream order)
+            out["stepped"] = self.optimizer.accum_pending >= self.accum_steps
+            if not out["stepped"]:
+                return out
         self.scaler.step(self.optimizer)                           # model/trainer.py:122-123 (update() is part of the device-side step)
         self.scaler.update()
         if self.optimizer.clipping:
             out["grad_norm"] = self.optimizer.last_grad_norm
         return out
+
+    def flush_accumulated(self) -> bool:
+        """Step an open accumulation cycle now, on the mean of the micro-steps it holds (the end of an epoch whose length is no multiple of
+        accum_steps; before a checkpoint).  False when no cycle is open."""
+        if self.optimizer.accum_pending == 0:
+            return False
+        self.scaler.step(self.optimizer)
+        self.scaler.update()
+        return True
 
     def _reduce_head_early(self):
         # hook at the start of the wav2vec2 backward: valid only when this step made ONE fusion / decoder call (a batch whose two lip
@@ -468,7 +486,8 @@ class MultimodalTrainer:
                     print(f"[Batch {batch_idx}] CTC1: {out['loss1'].item():.4f}, CTC2: {out['loss2'].item():.4f}, "
                           f"Contrast1: {float(out['contrast1']):.4f}, Contrast2: {float(out['contrast2']):.4f}, "
                           f"Total: {out['total'].item():.4f}", flush=True)
-                    if self.optimizer.clipping or self.optimizer.scheduled:
+                    # the last optimizer step's; with accum_steps > 1 none may have been taken yet (the state block is made by the first)
+                    if (self.optimizer.clipping or self.optimizer.scheduled) and self.optimizer.last_grad_norm is not None:
                         print(f"[Batch {batch_idx}] grad norm: {float(self.optimizer.last_grad_norm):.4f}, "
                               f"LR multiplier: {float(self.optimizer.last_lr_mult):.4f}", flush=True)
             except NotImplementedError:  # a configuration this build does not cover: every later batch would fail the same way
@@ -479,6 +498,8 @@ class MultimodalTrainer:
                     # data parallel: a rank that skips a batch no longer issues the collectives its peers are waiting in
                     raise
                 continue
+        if self.accum_steps > 1:
+            self.flush_accumulated()                               # a loader whose length is no multiple of accum_steps: no cycle spans two epochs
         if self.native_ctc:
             self.fusion_module.drain_flag_check()                  # the last step's timeout words: nothing stays pending past the epoch
         return total_loss / max(1, len(dataloader))

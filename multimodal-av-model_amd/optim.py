@@ -5,7 +5,8 @@ un-scale) into the step so that no extra pass over the gradients is needed.  Opt
 ``total_steps``): global-norm gradient clipping and a linear warmup / decay schedule of the learning rate, decided on the device inside
 the same fused step.  Opt-in (``ema_decay``): an exponential moving average of the weights kept by that step, and
 ``swap_averaged`` / ``averaged`` to evaluate and save with it.  Opt-in (``weight_decay`` / ``lr_schedule="cosine"``):
-decoupled weight decay - torch.optim.AdamW's law - and a warmup + cosine schedule, inside the same step."""
+decoupled weight decay - torch.optim.AdamW's law - and a warmup + cosine schedule, inside the same step.  Opt-in
+(``accumulate()``): the gradients of several micro-batches summed on the device into one such step."""
 from __future__ import annotations
 
 import contextlib
@@ -204,6 +205,12 @@ class _Plan:
     __slots__ = ("sizes", "hyper", "ct", "cs", "slots", "nch", "n", "ptrs", "eo_n", "eo_nch", "eo_sizes", "eo_ct", "eo_cs", "ema", "wd")
 
 
+class _AccumPlan:
+    """Static part of one av_grad_accum_multi launch (cached per set of (parameter, mode)): sizes, chunk table, the mode of each tensor (0: its
+    first contribution of the cycle, a copy; 1: an add) - and the pointer table [n][2] = {grad, accumulator} of its last launch."""
+    __slots__ = ("sizes", "ct", "cs", "nch", "mode", "ptrs")
+
+
 class AvAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics, one fused launch per step whatever the set of parameters that received a gradient: step counts are
     PER TENSOR (torch keeps ``state[p]['step']`` per parameter; LayerDrop leaves a whole layer without gradients now and then,
@@ -228,6 +235,13 @@ class AvAdam(torch.optim.Optimizer):
     splitting groups.  ``lr_schedule="cosine"`` replaces the linear decay after the warmup by ``lr_multiplier(..., schedule="cosine")`` and
     needs ``total_steps``.
 
+    ``accumulate()`` folds every ``p.grad`` into an fp32 accumulator of its own with one launch (av_grad_accum_multi: a copy for a tensor's
+    first contribution of the cycle, an fp32 add after it - autograd's ``.grad +=``, bit for bit) and counts in ``accum_pending``.  The next
+    ``step()`` then runs on the accumulators of the parameters that contributed, at ``grad_scale / accum_pending`` (the mean over the
+    micro-batches; ``accum_mean=False``: the sum), and closes the cycle.  Everything above stays per optimizer step; a step the device skips
+    for an overflow discards the whole cycle, as torch's GradScaler with accumulation does.  Without a call of ``accumulate()`` nothing of
+    this runs and no accumulator exists.
+
     Every step is one call of ``av_adam_multi_wd`` with zeros and NULLs for what is off: by that function's contract this is
     ``av_adam_multi_ema`` without decay and cosine, ``av_adam_multi_ex`` without an EMA and ``av_adam_multi`` with clipping and schedule off as
     well - the same kernels are launched."""
@@ -236,7 +250,7 @@ class AvAdam(torch.optim.Optimizer):
     EMA_KEY = "av_ema_step"               # ... of the count of EMA updates
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, warmup_steps=0, total_steps=0, ema_decay=0.0,
-                 ema_warmup=False, weight_decay=0.0, decay_1d=False, lr_schedule="linear"):
+                 ema_warmup=False, weight_decay=0.0, decay_1d=False, lr_schedule="linear", accum_mean=True):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=check_weight_decay(weight_decay)))
         self.max_grad_norm, self.warmup_steps, self.total_steps = check_clip_schedule(max_grad_norm, warmup_steps, total_steps)
         self.lr_schedule, self.decay_1d = lr_schedule, bool(decay_1d)
@@ -254,6 +268,12 @@ class AvAdam(torch.optim.Optimizer):
         self._steps_seeded = False
         self._keep = None             # the last step's gradients, alive until the next step (stream-ordered use)
         self.fused_launches = 0       # diagnostics / tests: every step is one av_adam_multi_wd call
+        self.accum_mean = bool(accum_mean)
+        self.accum_pending = 0        # accumulate() calls of the open cycle (0: none is open)
+        self._accum = {}              # parameter -> its fp32 accumulator, made at its first contribution (not in self.state: not saved)
+        self._accum_open = set()      # id(parameter) of those that contributed to the open cycle: host knowledge, like p.grad is None
+        self._accum_plans = {}
+        self._accum_keep = None       # the last accumulate()'s gradients, alive until the next one
 
     CHUNK = 65536
 
@@ -379,6 +399,7 @@ class AvAdam(torch.optim.Optimizer):
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"])
         self._steps_seeded = False                                  # the device table is re-seeded from the loaded counts
+        self._close_cycle()                                         # an open accumulation cycle belongs to the state that was replaced
 
     def reset_state(self) -> None:
         """Forget moments and step counts (a fresh optimizer over the same parameters)."""
@@ -388,6 +409,7 @@ class AvAdam(torch.optim.Optimizer):
         self._clip_state.set_counter(0)
         self._ema_state.set_counter(0)
         self._swapped = False
+        self._close_cycle()
 
     def state_dict(self):
         """torch.optim.Adam's format.  Under loss scaling only the device table knows the per-parameter step counts (overflowing steps are
@@ -411,6 +433,7 @@ class AvAdam(torch.optim.Optimizer):
         self._steps_dev = None
         self._steps_seeded = False
         self._plans = {}
+        self._accum_plans = {}
         self._clip_ws = None                                        # sized by the chunks of all parameters
 
     def _plan(self, plist, dev, ema_only=None, decays=None) -> _Plan:
@@ -452,10 +475,11 @@ class AvAdam(torch.optim.Optimizer):
                 if st and "step" in st:
                     st["step"] = int(host[slots[id(p)]])
 
-    def _collect(self):
+    def _collect(self, contributed=None):
         """(plist, ema_only, decays): (parameter, {lr, beta1, beta2, eps}, state) of every parameter with a gradient, its state created at
         its first step; with an EMA, the parameters that have an average and no gradient in this step (still moved towards p), else None;
-        the weight decay of each tensor of plist, or None when none of them is decayed."""
+        the weight decay of each tensor of plist, or None when none of them is decayed.  ``contributed`` (a step that closes an accumulation
+        cycle): the ids of the parameters that count as having a gradient, whatever their ``p.grad`` is now."""
         plist, decays = [], []
         ema_only = [] if self.averaging else None
         for group in self.param_groups:
@@ -463,7 +487,7 @@ class AvAdam(torch.optim.Optimizer):
             hp = (float(group["lr"]), float(b1), float(b2), float(group["eps"]))
             wd = check_weight_decay(group.get("weight_decay", self.defaults["weight_decay"]))
             for p in group["params"]:
-                if p.grad is None:
+                if (p.grad is None) if contributed is None else (id(p) not in contributed):
                     if ema_only is not None and "ema" in self.state.get(p, ()):
                         ema_only.append(p)
                     continue
@@ -493,7 +517,7 @@ class AvAdam(torch.optim.Optimizer):
                 eflat += [p.data_ptr(), self.state[p]["ema"].data_ptr()]
             pl.ema.upload(eflat)
 
-    def _launch(self, pl, steps, scaler, dev) -> None:
+    def _launch(self, pl, steps, scaler, dev, grad_scale) -> None:
         """The one native call of a step.  Whatever is off is passed as zeros and NULLs."""
         scale = (None, 1.0, 1.0, 1) if scaler is None else (ops.ptr(scaler.state), scaler.growth_factor, scaler.backoff_factor,
                                                             scaler.growth_interval)
@@ -504,7 +528,7 @@ class AvAdam(torch.optim.Optimizer):
             ema = (ops.ptr(pl.ema.dev), only, ops.ptr(pl.eo_sizes), ops.ptr(pl.eo_ct), ops.ptr(pl.eo_cs), pl.eo_nch, self.ema_decay,
                    int(self.ema_warmup), ops.ptr(self._ema_state.on(dev)))
         L.check(L.lib().av_adam_multi_wd(ops.ptr(pl.ptrs.dev), ops.ptr(pl.sizes), ops.ptr(pl.hyper), ops.ptr(pl.ct), ops.ptr(pl.cs), pl.nch,
-                                         self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(self.grad_scale), *scale,
+                                         self.CHUNK, ops.ptr(steps), ops.ptr(pl.slots), pl.n, float(grad_scale), *scale,
                                          self.max_grad_norm, self.warmup_steps, self.total_steps, ops.ptr(ws),
                                          ws.numel() * ws.element_size() if ws is not None else 0, ops.ptr(cstate), *ema, ops.ptr(pl.wd),
                                          self._lr_schedule, ops.stream()),
@@ -512,25 +536,88 @@ class AvAdam(torch.optim.Optimizer):
         self.fused_launches += 1
 
     def step(self, closure=None, scaler: "AvGradScaler" = None):
-        """One fused multi-tensor launch for all parameters that have a gradient (per-tensor step counts, per-group lr / betas / eps)."""
+        """One fused multi-tensor launch for all parameters that have a gradient (per-tensor step counts, per-group lr / betas / eps).
+        After ``accumulate()``: for the parameters that contributed to the open cycle, on their accumulators, and the cycle is closed."""
         if self._swapped:
             raise RuntimeError("AvAdam.step: the parameters hold the averaged weights (swap_averaged); swap back before stepping")
         loss = closure() if closure is not None else None
+        if self.accum_pending > 0:
+            return self._step_accumulated(loss, scaler)
         plist, ema_only, decays = self._collect()
         if not plist:
             return loss
         params = [p for p, _, _ in plist]
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
+        self._step_on(plist, ema_only, decays, grads, scaler, self.grad_scale)
+        return loss
+
+    def _step_accumulated(self, loss, scaler):
+        """The step that closes an accumulation cycle.  The device may skip it for an overflow; the host neither knows nor needs to: the cycle
+        is closed either way."""
+        plist, ema_only, decays = self._collect(self._accum_open)
+        if plist:
+            scale = self.grad_scale / self.accum_pending if self.accum_mean else self.grad_scale
+            self._step_on(plist, ema_only, decays, [self._accum[p] for p, _, _ in plist], scaler, scale)
+        self._close_cycle()
+        return loss
+
+    def _step_on(self, plist, ema_only, decays, grads, scaler, grad_scale) -> None:
+        """The fused step of ``plist`` on ``grads`` (contiguous fp32, one per tensor)."""
+        params = [p for p, _, _ in plist]
         dev = params[0].device
         steps = self._step_table(dev)                               # BEFORE the host counts move: a fresh table is seeded from them
         pl = self._plan(plist, dev, ema_only, decays)
-        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
         shadows = shadow.lookup_many(params)                        # bf16 compute copies (perf path), written by the kernel
         self._bind(pl, plist, ema_only, grads, shadows)
-        self._launch(pl, steps, scaler, dev)
+        self._launch(pl, steps, scaler, dev, grad_scale)
         if scaler is None:
             for _, _, st in plist:                                  # exact host mirror (with a scaler the device decides: sync_steps)
                 st["step"] = int(st["step"]) + 1
         self._keep = grads                                          # alive until the next step (stream-ordered use)
         torch.autograd.graph.increment_version(params)              # other compute-dtype caches (re-layouts) rebuild
         shadow.mark_fresh([p for p, sh in zip(params, shadows) if sh is not None])      # ... the shadows were just written
-        return loss
+
+    def _close_cycle(self) -> None:
+        self.accum_pending = 0
+        self._accum_open.clear()
+        self._accum_keep = None
+
+    def _accum_plan(self, ps, modes, dev) -> _AccumPlan:
+        key = tuple((p.data_ptr(), p.numel(), m) for p, m in zip(ps, modes))
+        pl = self._accum_plans.get(key)
+        if pl is None:
+            if len(self._accum_plans) >= 64:                        # LayerDrop patterns, as in _plan
+                self._accum_plans.clear()
+            pl = _AccumPlan()
+            pl.sizes, pl.ct, pl.cs, pl.nch = _size_tables([p.numel() for p in ps], self.CHUNK, dev)
+            pl.mode = ops.h2d_async(np.asarray(modes, dtype=np.int32), dev)
+            pl.ptrs = _PtrTable(2 * len(ps), dev)
+            self._accum_plans[key] = pl
+        return pl
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """One micro-step: ``p.grad`` of every parameter that has one goes into that parameter's accumulator in one launch
+        (av_grad_accum_multi) - copied if it is the parameter's first contribution of the open cycle, added in fp32 otherwise, which is the
+        order and rounding of autograd's ``.grad +=`` - and ``accum_pending`` counts the call.  Nothing synchronises.  The gradients may be
+        overwritten once the call has returned (stream order)."""
+        ps = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if ps:
+            if any(not p.is_cuda or p.dtype != torch.float32 for p in ps):
+                raise RuntimeError("AvAdam: parameters must be float32 CUDA tensors (no CPU fallback)")
+            dev = ps[0].device
+            modes = [1 if id(p) in self._accum_open else 0 for p in ps]
+            for p in ps:
+                if p not in self._accum:
+                    self._accum[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
+            pl = self._accum_plan(ps, modes, dev)
+            grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
+            flat = []
+            for p, g in zip(ps, grads):
+                flat += [g.data_ptr(), self._accum[p].data_ptr()]
+            pl.ptrs.upload(flat)
+            L.check(L.lib().av_grad_accum_multi(ops.ptr(pl.ptrs.dev), ops.ptr(pl.mode), ops.ptr(pl.sizes), ops.ptr(pl.ct), ops.ptr(pl.cs),
+                                                pl.nch, self.CHUNK, ops.stream()), "av_grad_accum_multi")
+            self._accum_keep = grads                                # alive until the next call (stream-ordered use)
+            self._accum_open.update(id(p) for p in ps)
+        self.accum_pending += 1
