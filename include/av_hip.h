@@ -436,6 +436,28 @@ int av_ctc_span_conf(const float* conf, const int* spans, const long long* lengt
 int av_ctc_greedy_timed(const float* log_probs, long long stride_b, long long stride_t, const long long* lengths, int B, int T, int V,
                         int blank, int method, float alpha, int aggregation, int* out_ids, int* out_len, int* out_span,
                         float* token_conf, float* frame_conf, void* stream);
+/* Long-form transcription on the device (csrc/ctc_longform.hip; longform.py holds the window plan and restates the three laws in float32
+ * numpy): fp32, no atomics, no synchronisation, every output element written, cuts and lengths stay in DEVICE memory.
+ * S is the speaker axis; rows are addressed as base + s * stride_s + row * stride_r (floats), stride_r >= V, rows contiguous.
+ * av_ctc_stitch: windows = the R = nw * W rows of every speaker's window log-probs; src_row int32 [F][4] and src_weight fp32 [F][4]: per
+ *   output frame its 1 .. 4 source rows in ascending window order (-1 = none, packed in front) and their normalised weights -> out fp32
+ *   [S][F][V].  One source: the row copied bit for bit.  n > 1 sources, per class: M = max_k x_k, out = M + log(sum_k wn_k exp(x_k - M))
+ *   in source order; M = -inf gives -inf, a NaN source gives NaN.  (The "centre" policy is a table with one source per frame.)  A frame
+ *   without a source is filled with -inf.
+ * av_ctc_cut_points: log_probs [S][F][V], N = segment - 2 radius >= 2 radius + 1, segment <= 408; nb = number of j >= 1 with
+ *   j N + radius < F -> cuts int32 [S][nb + 2]: cuts[0] = 0, cuts[nb + 1] = F, cuts[j] = the frame t of [j N - radius, j N + radius]
+ *   intersected with [1, F - 1] with the largest log_probs[t][blank] (fp32 compare, a NaN ranks as -inf, ties go to the smallest t).
+ * av_ctc_segment_gather: cuts as above (clamped to [0, F] and made monotone, a segment cut at `segment` frames) -> seg_log_probs fp32
+ *   [S * (nb + 1)][segment][V]: row i of segment j is log_probs[cuts[j] + i] for i < cuts[j + 1] - cuts[j] and 0.0 after it;
+ *   seg_lengths int64 [S * (nb + 1)]: the lengths the other CTC entries of this header read from device memory. */
+#define AV_LONGFORM_MAX_SOURCES 4
+#define AV_LONGFORM_MAX_SEGMENT 408
+int av_ctc_stitch(const float* windows, long long stride_s, long long stride_r, const int* src_row, const float* src_weight, int S, int R,
+                  int F, int V, float* out, void* stream);
+int av_ctc_cut_points(const float* log_probs, long long stride_s, long long stride_t, int S, int F, int V, int blank, int segment, int radius,
+                      int* cuts, void* stream);
+int av_ctc_segment_gather(const float* log_probs, long long stride_s, long long stride_t, const int* cuts, int S, int F, int V, int nb,
+                          int segment, float* seg_log_probs, long long* seg_lengths, void* stream);
 /* Word, character and token error counts on the device: edit distance with operation counts between ONE reference and N hypotheses per
  * utterance, from token ids through a device copy of the tokenizer's piece table - what MultimodalTrainer.evaluate() measures
  * (word_error_rate of model/trainer.py, the jiwer.wer stand-in), plus the character and token levels and the S / D / I breakdown.

@@ -61,6 +61,15 @@ OPTIONS = {
     "conf_method": ("AVAMD_CONF_METHOD", str, "tsallis", str),
     "conf_alpha": ("AVAMD_CONF_ALPHA", float, "0.33", float),
     "conf_aggregation": ("AVAMD_CONF_AGG", str, "min", str),
+    # transcribe_long() (longform.py), read by it alone: lip frames per window and discarded per window side, how overlapping windows are
+    # joined ("centre": the owner's rows; "average": the weighted mean of the posteriors), windows per forward call, and the longest segment
+    # of the stitched sequence with the half-width of the zone in which its cut is searched
+    "long_window": ("AVAMD_LONG_WINDOW", int, "100", int),
+    "long_stride": ("AVAMD_LONG_STRIDE", int, "12", int),
+    "long_policy": ("AVAMD_LONG_POLICY", str, "centre", str),
+    "long_batch": ("AVAMD_LONG_BATCH", int, "16", int),
+    "long_segment": ("AVAMD_LONG_SEGMENT", int, "400", int),
+    "long_radius": ("AVAMD_LONG_RADIUS", int, "50", int),
 }
 
 
@@ -88,6 +97,19 @@ def check_confidence(method: str, alpha: float, aggregation: str) -> None:
     from ..confidence import check_aggregation, check_method
     check_method("conf_method / conf_alpha", method, alpha)
     check_aggregation("conf_aggregation", aggregation)
+
+
+def check_longform(window: int, stride: int, policy: str, batch: int, segment: int, radius: int) -> None:
+    from ..longform import MAX_SOURCES, POLICIES, check_plan, check_segment, min_average_hop
+    hop = check_plan(window, stride)
+    check_segment(segment, radius)
+    if policy not in POLICIES:
+        raise ValueError(f"long_policy must be one of {POLICIES}, got {policy!r}")
+    if policy == "average" and hop < min_average_hop(window):
+        raise ValueError(f"long_policy='average' joins at most {MAX_SOURCES} windows per frame: long_window={window} needs a hop of at least "
+                         f"{min_average_hop(window)}, long_window - 2 long_stride is {hop}")
+    if batch < 1:
+        raise ValueError(f"long_batch must be >= 1, got {batch}")
 
 
 def check_ema(eval_ema: bool, ema_decay: float) -> None:

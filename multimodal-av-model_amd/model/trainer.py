@@ -72,7 +72,9 @@ class MultimodalTrainer:
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, ema_decay: Optional[float] = None,
                  ema_warmup: Optional[bool] = None, eval_ema: Optional[bool] = None, augment=None, conf_method: Optional[str] = None,
                  conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None, weight_decay: Optional[float] = None,
-                 lr_schedule: Optional[str] = None, accum_steps: Optional[int] = None):
+                 lr_schedule: Optional[str] = None, accum_steps: Optional[int] = None, long_window: Optional[int] = None,
+                 long_stride: Optional[int] = None, long_policy: Optional[str] = None, long_batch: Optional[int] = None,
+                 long_segment: Optional[int] = None, long_radius: Optional[int] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -95,6 +97,10 @@ class MultimodalTrainer:
         self.conf_method, self.conf_alpha = opt("conf_method", conf_method), opt("conf_alpha", conf_alpha)
         self.conf_aggregation = opt("conf_aggregation", conf_aggregation)
         options.check_confidence(self.conf_method, self.conf_alpha, self.conf_aggregation)
+        self.long_window, self.long_stride = opt("long_window", long_window), opt("long_stride", long_stride)
+        self.long_policy, self.long_batch = opt("long_policy", long_policy), opt("long_batch", long_batch)
+        self.long_segment, self.long_radius = opt("long_segment", long_segment), opt("long_radius", long_radius)
+        options.check_longform(self.long_window, self.long_stride, self.long_policy, self.long_batch, self.long_segment, self.long_radius)
         self.mwer_weight, self.mwer_nbest = opt("mwer_weight", mwer_weight), opt("mwer_nbest", mwer_nbest)
         self.mwer_beam, self.mwer_level = opt("mwer_beam", mwer_beam), mwer_level
         options.check_mwer(self.mwer_weight, self.mwer_nbest, self.mwer_beam, mwer_level)
@@ -649,17 +655,18 @@ class MultimodalTrainer:
             self.fusion_module.drain_flag_check()                  # raises if a persistent BiLSTM launch timed out
         return tuple(self._transcribe_host(h, B, T, nbest, frame_rate) for h in host)
 
-    def _transcribe_device(self, lp, nbest):
+    def _transcribe_device(self, lp, nbest, input_lengths=None):
         """One speaker's log-probs [B, T, V] -> flat int32 block on the device: [B][T + 1][5] = per token (id, first frame, end frame, bits of
         its confidence, bits of its path score), the last row (number of tokens, bits of the utterance confidence, 0, 0, 0); with a beam then
-        [B][nbest][T + 2] = per hypothesis its ids, its length and the bits of its score."""
+        [B][nbest][T + 2] = per hypothesis its ids, its length and the bits of its score.  ``input_lengths`` (transcribe_long's segments):
+        int64 [B] on the device, read there by every pass; None decodes all T frames."""
         from ..beam_search import nbest_on_device
         from ..confidence import frame_confidence, greedy_timed, span_confidence, utterance_confidence
         blank, (B, T, _) = self.tokenizer.blank_id, lp.shape
         method, alpha, agg = self.conf_method, self.conf_alpha, self.conf_aggregation
         i32 = lambda x: x.contiguous().view(torch.int32)       # noqa: E731
         if self.eval_beam_width == 0:
-            g = greedy_timed(lp, blank, None, method, alpha, agg)
+            g = greedy_timed(lp, blank, input_lengths, method, alpha, agg)
             ids, n, spans, tc, ts, extra = g.ids, g.lengths, g.spans, g.token_conf, self._greedy_token_scores(lp, g), []
         else:
             kw = {}
@@ -667,10 +674,12 @@ class MultimodalTrainer:
                 kw.update(lm=self.eval_lm, lm_weight=self.eval_lm_weight, token_bonus=self.eval_token_bonus)
             if self.eval_bias is not None:
                 kw.update(bias=self.eval_bias, bias_weight=self.eval_bias_weight)
+            if input_lengths is not None:
+                kw.update(lengths=input_lengths)
             hyp, hl, hs = nbest_on_device(lp, self.eval_beam_width, blank, nbest=nbest, **kw)[:3]
             ids, n = hyp[:, 0], hl[:, 0].clamp_min(0)
-            al = forced_align(lp, ids, None, n, blank=blank)
-            tc = span_confidence(frame_confidence(lp, None, method, alpha), al.spans, None, agg)
+            al = forced_align(lp, ids, input_lengths, n, blank=blank)
+            tc = span_confidence(frame_confidence(lp, input_lengths, method, alpha), al.spans, input_lengths, agg)
             spans, ts, extra = al.spans, al.token_scores, [torch.cat([hyp, hl[..., None], i32(hs)[..., None]], 2).reshape(-1)]
         utt = utterance_confidence(tc, n, agg)
         tail = torch.zeros((B, 1, 5), dtype=torch.int32, device=lp.device)
@@ -711,3 +720,105 @@ class MultimodalTrainer:
                               for k in range(nbest) if int(hyps[i, k, T]) >= 0]
             res.append(r)
         return res
+
+    # ---- transcription of a recording of any length: overlapping windows, stitched and cut on the device (longform.py) ----
+    def transcribe_long(self, recording, frame_rate: float = 25.0, nbest: int = 1):
+        """Both speakers' transcripts of ONE recording of any length: ``audio`` [n] or [1, n], ``lip1`` / ``lip2`` [F, 1, H, W] or
+        [1, F, 1, H, W], on the host or the device; F comes from the lips (which must agree), the audio is cut or zero-padded to 640 F.
+        The recording is covered with windows of ``long_window`` lip frames (longform.plan_windows: ``long_stride`` frames per side are
+        discarded, no window is padded), they go through forward_log_probs ``long_batch`` at a time in eval mode (the averaged weights
+        under ``eval_ema``) into one [2, nw, W, V] device buffer, are stitched by ``long_policy`` into [2, F, V], cut at blank frames into
+        segments of at most ``long_segment`` frames (cuts searched within ``long_radius`` frames) and decoded in ONE batch of segments as
+        transcribe() decodes (``eval_beam_width``, ``eval_lm``, ``eval_bias``, ``conf_*``); the decoders read the segment lengths on the
+        device.  F <= ``long_segment`` is not cut, so F <= ``long_window`` too is what transcribe() computes for that clip.  The cuts ride
+        in the decode's int32 block: ONE transfer at the end and no synchronisation before it.
+        Returns (result1, result2), a dict per speaker: ``text``, ``ids``, ``confidence`` (``conf_aggregation`` over ALL tokens in order,
+        confidence.host_span_law in float32), ``words`` (transcribe()'s, times counted from the start of the recording; a word may span a
+        cut) and ``segments``: per segment ``start``, ``end`` (seconds), ``text``, ``confidence`` and, with a beam, ``nbest``.
+        A run of equal argmax frames across a cut that is not at an argmax-blank frame may be emitted twice, and a language model or a
+        phrase match restarts at every segment (longform.py).  There is no limit on F other than memory."""
+        from .. import longform
+        from ..confidence import host_span_law
+        nbest, Wb = int(nbest), self.eval_beam_width
+        if not 1 <= nbest <= max(Wb, 1):
+            raise ValueError(f"transcribe_long: need 1 <= nbest <= max(eval_beam_width, 1), got nbest={nbest} with eval_beam_width={Wb}")
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("MultimodalTrainer.transcribe_long: the model runs on the GPU; there is no CPU fallback")
+        audio, lip1, lip2 = self._recording(recording)
+        F_, seg, rad = lip1.shape[0], self.long_segment, self.long_radius
+        plan = longform.plan_windows(F_, self.long_window, self.long_stride)
+        plan.sources(self.long_policy)                             # a plan the policy cannot join raises before anything runs
+        Wd, nw, buf = plan.width, plan.count, None
+        with self._inference():
+            mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+            modes = [(sm, sm.training) for m in mods for sm in m.modules()]
+            for m in mods:
+                m.eval()
+            try:
+                for k0 in range(0, nw, self.long_batch):
+                    ks = range(k0, min(k0 + self.long_batch, nw))
+                    out = self.forward_log_probs({
+                        "audio": torch.stack([audio[slice(*plan.audio_window(k))] for k in ks]),
+                        "lip1": torch.stack([lip1[plan.starts[k]:plan.starts[k] + Wd] for k in ks]),
+                        "lip2": torch.stack([lip2[plan.starts[k]:plan.starts[k] + Wd] for k in ks])})
+                    self.fusion_module.stage_flag_check()
+                    for s, spk in enumerate(("1", "2")):
+                        lp = out["log_probs" + spk]
+                        if lp.shape[1] != Wd:
+                            raise RuntimeError(f"transcribe_long: a window of {Wd} lip frames came back with {lp.shape[1]} CTC frames")
+                        if buf is None:
+                            buf = torch.empty((2, nw, Wd, lp.shape[2]), dtype=torch.float32, device=lp.device)
+                        buf[s, k0:k0 + len(ks)].copy_(lp)
+            finally:
+                for sm, was in modes:
+                    sm.training = was
+            stitched = longform.stitch(buf, plan, self.long_policy)
+            if F_ <= seg:                                          # one segment per speaker: exactly what transcribe() decodes
+                cuts = ops.h2d_async(torch.tensor([[0, F_]] * 2, dtype=torch.int32).numpy(), stitched.device)
+                flat, T = self._transcribe_device(stitched, nbest), F_
+            else:
+                cuts = longform.cut_points(stitched, self.tokenizer.blank_id, seg, rad)
+                seg_lp, seg_len = longform.split_segments(stitched, cuts, seg)
+                flat, T = self._transcribe_device(seg_lp, nbest, seg_len), seg
+            host = torch.cat([flat, cuts.reshape(-1)]).cpu()       # the only transfer
+            self.fusion_module.drain_flag_check()                  # raises if a persistent BiLSTM launch timed out
+        ns = cuts.shape[1] - 1                                     # segments per speaker
+        cuts_h = host[-2 * (ns + 1):].view(2, ns + 1).tolist()
+        segs = self._transcribe_host(host[:-2 * (ns + 1)], 2 * ns, T, nbest, frame_rate)
+        main = host[:2 * ns * (T + 1) * 5].view(2 * ns, T + 1, 5)
+        f32 = lambda x: x.contiguous().view(torch.float32)         # noqa: E731
+        res = []
+        for s in range(2):
+            ids, spans, tc, ts, parts = [], [], [], [], []
+            for j in range(ns):
+                i, c0, c1 = s * ns + j, cuts_h[s][j], cuts_h[s][j + 1]
+                n, r = int(main[i, T, 0]), segs[i]
+                ids += r["ids"]
+                sp = main[i, :n, 1:3]
+                spans.append(torch.where(sp < 0, sp, sp + c0))      # a token that could not be aligned keeps its -1
+                tc.append(f32(main[i, :n, 3])); ts.append(f32(main[i, :n, 4]))
+                parts.append({"start": c0 / frame_rate, "end": c1 / frame_rate, "text": r["text"], "confidence": r["confidence"]})
+                if "nbest" in r:
+                    parts[-1]["nbest"] = r["nbest"]
+            spans, tc, ts = torch.cat(spans), torch.cat(tc), torch.cat(ts)
+            conf = float(host_span_law(tc.numpy(), 0, len(ids), len(ids), self.conf_aggregation)) if ids else 0.0
+            res.append({"text": fast_decode(ids, self.tokenizer), "ids": ids, "confidence": conf,
+                        "words": word_segments(self.tokenizer, ids, spans, ts, frame_rate, token_conf=tc, aggregation=self.conf_aggregation),
+                        "segments": parts})
+        return tuple(res)
+
+    @staticmethod
+    def _recording(recording):
+        """-> (audio [640 F], lip1 [F, 1, H, W], lip2 [F, 1, H, W]), each on the side it came from."""
+        audio, lips = recording["audio"], [recording["lip1"], recording["lip2"]]
+        if audio.dim() == 2 and audio.shape[0] == 1:
+            audio = audio[0]
+        lips = [x[0] if x.dim() == 5 and x.shape[0] == 1 else x for x in lips]
+        if audio.dim() != 1 or any(x.dim() != 4 or x.shape[1] != 1 for x in lips):
+            raise ValueError("transcribe_long: need audio [n] or [1, n] and lip1 / lip2 [F, 1, H, W] or [1, F, 1, H, W], got "
+                             f"{tuple(recording['audio'].shape)}, {tuple(recording['lip1'].shape)} and {tuple(recording['lip2'].shape)}")
+        if lips[0].shape != lips[1].shape or lips[0].shape[0] < 1:
+            raise ValueError(f"transcribe_long: lip1 {tuple(lips[0].shape)} and lip2 {tuple(lips[1].shape)} must agree and hold a frame")
+        n = host_meta.AUDIO_PER_LIP_FRAME * lips[0].shape[0]
+        audio = audio[:n] if audio.shape[0] >= n else F.pad(audio, (0, n - audio.shape[0]))
+        return audio, lips[0], lips[1]

@@ -879,3 +879,65 @@ def ctc_greedy_timed(log_probs: Tensor, blank: int, lengths=None, method: str = 
     L.check(L.lib().av_ctc_greedy_timed(ptr(lp), sb, st, ptr(ln), B, T, V, blank, m, alpha, a, ptr(ids), ptr(cnt), ptr(spans), ptr(tok),
                                         ptr(conf), stream()), "av_ctc_greedy_timed")
     return ids, cnt, spans, tok, conf
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Long-form transcription on the device (csrc/ctc_longform.hip; the window plan, the laws and the host path: longform.py).  Cuts and
+# lengths stay on the device, nothing in a call synchronises.
+# ---------------------------------------------------------------------------------------------------------------
+def _longform_rows(who: str, lp, inner: int):
+    """A float32 GPU block [S, ..., V] whose ``inner`` middle dimensions collapse into one row axis -> (view with contiguous rows, stride
+    between speakers, stride between rows); a view that does not collapse, or whose rows are not contiguous, is copied."""
+    if not isinstance(lp, Tensor) or not lp.is_cuda:
+        raise RuntimeError(f"{who} (HIP): the log-probs must be on the GPU; there is no CPU fallback (longform.py runs host tensors)")
+    if lp.dim() != 2 + inner:
+        raise ValueError(f"{who}: the log-probs must have {2 + inner} dimensions, got shape {tuple(lp.shape)}")
+    if lp.dtype != torch.float32:
+        raise TypeError(f"{who}: the log-probs must be float32, got {lp.dtype}")
+    lp = lp.detach()
+    if lp.stride(-1) != 1 or lp.stride(-2) < lp.shape[-1] or (inner == 2 and lp.stride(1) != lp.shape[2] * lp.stride(2)) \
+            or (lp.shape[0] > 1 and lp.stride(0) < lp.stride(-2) * lp.shape[1:-1].numel()):
+        lp = lp.contiguous()
+    return lp, lp.stride(0), lp.stride(-2)
+
+
+def ctc_stitch(window_log_probs: Tensor, src_row: Tensor, src_weight: Tensor, F: int) -> Tensor:
+    """av_ctc_stitch: ``window_log_probs`` fp32 [S, nw, W, V] (a view whose window rows are evenly spaced is taken without a copy),
+    ``src_row`` int32 [F, 4] and ``src_weight`` fp32 [F, 4] on the device (longform.WindowPlan.table) -> fp32 [S, F, V]."""
+    lp, ss, sr = _longform_rows("ctc_stitch", window_log_probs, 2)
+    S, nw, W, V = lp.shape
+    if V < 2 or nw * W < 1 or F < 1:
+        raise ValueError(f"ctc_stitch: need V >= 2 and at least one window row and frame, got shape {tuple(lp.shape)} F={F}")
+    if tuple(src_row.shape) != (F, 4) or src_row.dtype != torch.int32 or tuple(src_weight.shape) != (F, 4) or src_weight.dtype != torch.float32:
+        raise ValueError(f"ctc_stitch: the source table must be int32 [F={F}, 4] and float32 [F={F}, 4]")
+    _req(src_row, "ctc_stitch"); _req(src_weight, "ctc_stitch")
+    out = torch.empty((S, F, V), dtype=torch.float32, device=lp.device)
+    L.check(L.lib().av_ctc_stitch(ptr(lp), ss, sr, ptr(src_row.contiguous()), ptr(src_weight.contiguous()), S, nw * W, F, V, ptr(out), stream()),
+            "av_ctc_stitch")
+    return out
+
+
+def ctc_cut_points(log_probs: Tensor, blank: int, segment: int, radius: int, nb: int) -> Tensor:
+    """av_ctc_cut_points: ``log_probs`` fp32 [S, F, V] (any view with contiguous rows) -> cuts int32 [S, nb + 2] on the device; ``nb`` is
+    longform.boundaries(F, segment, radius), which the library recomputes."""
+    lp, ss, st = _longform_rows("ctc_cut_points", log_probs, 1)
+    S, F, V = lp.shape
+    cuts = torch.empty((S, nb + 2), dtype=torch.int32, device=lp.device)
+    L.check(L.lib().av_ctc_cut_points(ptr(lp), ss, st, S, F, V, int(blank), int(segment), int(radius), ptr(cuts), stream()), "av_ctc_cut_points")
+    return cuts
+
+
+def ctc_segment_gather(log_probs: Tensor, cuts: Tensor, segment: int):
+    """av_ctc_segment_gather: ``log_probs`` fp32 [S, F, V], ``cuts`` int32 [S, nb + 2] on the device -> (seg_lp fp32 [S (nb + 1), segment, V],
+    seg_len int64 [S (nb + 1)]), both on the device and fully written."""
+    lp, ss, st = _longform_rows("ctc_segment_gather", log_probs, 1)
+    S, F, V = lp.shape
+    _req(cuts, "ctc_segment_gather")
+    if cuts.dim() != 2 or cuts.shape[0] != S or cuts.shape[1] < 2 or cuts.dtype != torch.int32:
+        raise ValueError(f"ctc_segment_gather: cuts must be int32 [S={S}, nb + 2], got {cuts.dtype} {tuple(cuts.shape)}")
+    nb = cuts.shape[1] - 2
+    seg = torch.empty((S * (nb + 1), int(segment), V), dtype=torch.float32, device=lp.device)
+    ln = torch.empty((S * (nb + 1),), dtype=torch.int64, device=lp.device)
+    L.check(L.lib().av_ctc_segment_gather(ptr(lp), ss, st, ptr(cuts.contiguous()), S, F, V, nb, int(segment), ptr(seg), ptr(ln), stream()),
+            "av_ctc_segment_gather")
+    return seg, ln
