@@ -71,8 +71,8 @@ typedef struct av_gemm_args {
     int batch_inner;
     long long oA, oB, oC;
     /* optional dropout in the epilogue (hf:628-633,565-572 hidden / activation dropout): after the activation and BEFORE the
-     * residual, v *= mask(seed, stream, m*ldc + n) in {0, 1/(1-p)}; with AV_ACT_MUL_GELU_GRAD the same mask multiplies the
-     * gradient.  drop_p = 0 disables it. */
+     * residual, v *= mask(seed, stream, idx) in {0, 1/(1-p)}, idx = the element's offset from C: batch offset (zo*oC + zi*sC, or
+     * z*sC with one level) + m*ldc + n; with AV_ACT_MUL_GELU_GRAD the same mask multiplies the gradient.  drop_p = 0 disables it. */
     float drop_p;
     unsigned int drop_stream;
     unsigned long long drop_seed;
@@ -89,6 +89,33 @@ typedef struct av_gemm_args {
     int cNF, cPM;
 } av_gemm_args;
 int av_gemm(const av_gemm_args* args, void* stream);
+
+/* Launch record of av_gemm: a test and diagnostic aid.  Every av_gemm call of a thread clears that thread's record and, when it launches
+ * a kernel, fills it in next to the launch; nothing reads it back inside the library, and no dispatch decision depends on it.  Tests assert
+ * it so that a case whose shape no longer reaches the kernel it was written for fails instead of silently testing another one. */
+#define AV_GEMM_KERNEL_NONE 0    /* no launch by the last call (M or N zero, or an error before the launch) */
+#define AV_GEMM_KERNEL_GENERIC 1 /* gemm.hip: 128 x bn tile; in16 = 16-bit operands (else fp32), bn = 64 / 128 */
+#define AV_GEMM_KERNEL_FAST128 2 /* gemm_fast.hip 128 x bn kernel: bn = its BNT (64 / 128), conv, akm, bkm = its template form */
+#define AV_GEMM_KERNEL_V2 3      /* 256 x 128 three-stage kernel */
+#define AV_GEMM_KERNEL_V4 4      /* 8-phase 256 x 256 kernel, plain form */
+#define AV_GEMM_KERNEL_V4_CONV 5 /* 8-phase kernel, implicit-im2col form */
+#define AV_GEMM_KERNEL_V4_KM 6   /* 8-phase kernel, both operands k-major */
+#define AV_GEMM_KERNEL_V6 7      /* four-wavefront kernel behind its switch */
+#define AV_GEMM_KERNEL_V7 8      /* persistent kernel: act, out_dtype, nm1 = its instantiation */
+typedef struct av_gemm_launch_info {
+    int kernel;              /* AV_GEMM_KERNEL_* */
+    int in16, bn;            /* generic / 128 x bn kernels */
+    int conv, akm, bkm;      /* operand form of the 128 x bn and 8-phase kernels */
+    int act, out_dtype, nm1; /* the v7 instantiation (act and out_dtype are filled in for every kernel; nm1 = 0 elsewhere) */
+    int bm_eff;              /* rows a row tile owns (v4 / v7: 160 .. 256; the tile height elsewhere) */
+    int nbM, nbN;            /* row and column tiles */
+    int nfull;               /* v4 / v7: tiles run whole; the nbM * nbN - nfull tiles after them run as four quadrant jobs each */
+    int grid_x, grid_z;      /* the launch grid */
+    int c_vec, r_vec, aux_vec; /* the fast path's FastFlags: 16-byte stores of C / C2, loads of R, loads of aux (0 on the generic kernel) */
+} av_gemm_launch_info;
+/* copies the calling thread's record; returns AV_OK, or AV_ERR_ARG for a null pointer */
+int av_gemm_last_launch(av_gemm_launch_info* out);
+
 /* out[i] = (accumulate ? out[i] : 0) + alpha * sum_s parts[s*stride + i], i < n (fp32): the split-K partials of av_gemm */
 int av_sum_slices(const float* parts, int n_slices, long long n, long long stride, float alpha, float* out, int accumulate,
                   void* stream);

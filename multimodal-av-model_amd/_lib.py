@@ -40,6 +40,24 @@ class GemmArgs(C.Structure):
     ]
 
 
+GEMM_KERNELS = ("none", "generic", "fast128", "v2", "v4", "v4_conv", "v4_km", "v6", "v7")        # AV_GEMM_KERNEL_*
+
+
+class GemmLaunchInfo(C.Structure):
+    """av_gemm_launch_info: which kernel the thread's last av_gemm call launched, and how (a test and diagnostic aid)."""
+    _fields_ = [(n, i32) for n in ("kernel", "in16", "bn", "conv", "akm", "bkm", "act", "out_dtype", "nm1", "bm_eff", "nbM", "nbN", "nfull",
+                                   "grid_x", "grid_z", "c_vec", "r_vec", "aux_vec")]
+
+
+def gemm_last_launch() -> dict:
+    """The launch record of the calling thread's last av_gemm call as a dict; ``kernel`` is its name from GEMM_KERNELS."""
+    r = GemmLaunchInfo()
+    check(lib().av_gemm_last_launch(C.byref(r)), "av_gemm_last_launch")
+    d = {n: getattr(r, n) for n, _ in GemmLaunchInfo._fields_}
+    d["kernel"] = GEMM_KERNELS[r.kernel]
+    return d
+
+
 class W2v2LayerArgs(C.Structure):
     _fields_ = [
         ("B", i32), ("T", i32), ("hidden", i32), ("heads", i32), ("inter", i32), ("lp", i32), ("gf", i32), ("stream_base", i32),
@@ -73,6 +91,7 @@ SIGNATURES = {
     "av_last_error": [],
     "av_version": [],
     "av_gemm": [C.POINTER(GemmArgs), vp],
+    "av_gemm_last_launch": [C.POINTER(GemmLaunchInfo)],
     "av_w2v2_layer_fwd": [C.POINTER(W2v2LayerArgs), vp],
     "av_w2v2_layer_bwd_dx": [C.POINTER(W2v2LayerBwdArgs), vp],
     "av_transpose": [vp, i32, vp, i32, i32, i32, ll, i32, vp],

@@ -8,11 +8,15 @@
 // the transposed products of the backward pass share one main loop (include/av_hip.h).
 #include "av_common.h"
 
+void av_gemm_note_launch(const av_gemm_launch_info& r);   // the launch record (below); gemm_fast.hip calls it too
+
 namespace {
 
 constexpr int BM = 128;
 constexpr int BK = 32;
 constexpr int NT = 256;
+
+thread_local av_gemm_launch_info g_last_launch = {};   // av_gemm_last_launch: written next to each launch, read by tests only
 
 template <typename T> struct Cfg;
 template <> struct Cfg<float> { static constexpr int LD = 36, VEC = 4; };   // LDS row = 144 B
@@ -350,6 +354,14 @@ int launch(const av_gemm_args& p, hipStream_t st, bool a_vec, bool b_vec) {
     const int nbM = av_cdiv(p.M, BM), nbN = av_cdiv(p.N, BN);
     dim3 grid((unsigned)(nbM * (long long)nbN), 1, (unsigned)p.batch);
     hipLaunchKernelGGL(kern, grid, dim3(NT), lds, st, p, nbN, a_vec, b_vec);
+    {
+        av_gemm_launch_info r = {};
+        r.kernel = AV_GEMM_KERNEL_GENERIC; r.in16 = sizeof(T) == 2; r.bn = BN;
+        r.conv = AMODE == AV_A_CONV2D || AMODE == AV_A_CONV3D1; r.akm = AMODE == AV_A_TRANS; r.bkm = BMODE == AV_B_KN;
+        r.act = p.act; r.out_dtype = p.out_dtype; r.bm_eff = BM; r.nbM = nbM; r.nbN = nbN; r.nfull = nbM * nbN;
+        r.grid_x = (int)grid.x; r.grid_z = (int)grid.z;
+        av_gemm_note_launch(r);
+    }
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -378,7 +390,16 @@ template <typename T> bool vec_ok2(const void* base, long long ld, long long s1,
 
 int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st);   // gemm_fast.hip; -1 = not eligible
 
+void av_gemm_note_launch(const av_gemm_launch_info& r) { g_last_launch = r; }
+
+extern "C" int av_gemm_last_launch(av_gemm_launch_info* out) {
+    AV_CHECK(out != nullptr, "av_gemm_last_launch: null pointer");
+    *out = g_last_launch;
+    return AV_OK;
+}
+
 extern "C" int av_gemm(const av_gemm_args* a, void* stream) {
+    g_last_launch = av_gemm_launch_info{};
     AV_CHECK(a != nullptr, "av_gemm: null args");
     const av_gemm_args& p = *a;
     AV_CHECK(p.A && p.B && p.C, "av_gemm: null operand pointer");

@@ -1976,6 +1976,19 @@ __global__ __launch_bounds__(V6_NT, 1) void gemm_nt_bf16_v6_kernel(const av_gemm
     AV_STAMP(3);
 }
 
+void av_gemm_note_launch(const av_gemm_launch_info& r);   // gemm.hip: the thread's launch record (av_gemm_last_launch), a test and diagnostic aid
+
+// host stores next to a launch; no decision reads them
+static void note_launch(int kernel, const av_gemm_args& p, const FastFlags& fl, int bn, bool conv, bool akm, bool bkm, int nm1, int bm_eff, int nbM,
+                        int nbN, int nfull, unsigned grid_x, unsigned grid_z) {
+    av_gemm_launch_info r = {};
+    r.kernel = kernel; r.in16 = 1; r.bn = bn; r.conv = conv; r.akm = akm; r.bkm = bkm;
+    r.act = p.act; r.out_dtype = p.out_dtype; r.nm1 = nm1; r.bm_eff = bm_eff; r.nbM = nbM; r.nbN = nbN; r.nfull = nfull;
+    r.grid_x = (int)grid_x; r.grid_z = (int)grid_z;
+    r.c_vec = fl.c_vec; r.r_vec = fl.r_vec; r.aux_vec = fl.aux_vec;
+    av_gemm_note_launch(r);
+}
+
 template <int BNT, bool CONV, bool AKM = false, bool BKM = false>
 int launch_fast(const av_gemm_args& p, hipStream_t st, const FastFlags& fl) {
     constexpr int STAGE = TILE_A + BNT * BK * 2;
@@ -1993,6 +2006,7 @@ int launch_fast(const av_gemm_args& p, hipStream_t st, const FastFlags& fl) {
     const int nbM = av_cdiv(p.M, BM), nbN = av_cdiv(p.N, BNT);
     dim3 grid((unsigned)(nbM * (long long)nbN), 1, (unsigned)p.batch);
     hipLaunchKernelGGL(kern, grid, dim3(NT), LDS, st, p, nbM, nbN, fl);
+    note_launch(AV_GEMM_KERNEL_FAST128, p, fl, BNT, CONV, AKM, BKM, 0, BM, nbM, nbN, nbM * nbN, grid.x, grid.z);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -2041,6 +2055,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
             const int nbM = av_cdiv(p.M, V4_BM), nbN = av_cdiv(p.N, V4_BN);
             hipLaunchKernelGGL((gemm_nt_bf16_v4_kernel<false, true>), dim3((unsigned)(nbM * nbN * p.batch), 1, 1), dim3(V4_NT), V4_LDS, st, p, nbM, nbN, fl,
                                nbM * nbN * p.batch, V4_BM);
+            note_launch(AV_GEMM_KERNEL_V4_KM, p, fl, V4_BN, false, true, true, 0, V4_BM, nbM, nbN, nbM * nbN * p.batch, (unsigned)(nbM * nbN * p.batch), 1);
             AV_LAUNCH_CHECK();
             return AV_OK;
         }
@@ -2068,6 +2083,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
         }
         const int nbM = av_cdiv(p.M, V4_BM), nbN = av_cdiv(p.N, V4_BN);
         hipLaunchKernelGGL(gemm_nt_bf16_v4_kernel<true>, dim3((unsigned)(nbM * nbN), 1, 1), dim3(V4_NT), V4_LDS, st, p, nbM, nbN, fl, nbM * nbN, V4_BM);
+        note_launch(AV_GEMM_KERNEL_V4_CONV, p, fl, V4_BN, true, false, false, 0, V4_BM, nbM, nbN, nbM * nbN, (unsigned)(nbM * nbN), 1);
         AV_LAUNCH_CHECK();
         return AV_OK;
     }
@@ -2083,6 +2099,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
         }
         const int nbM = av_cdiv(p.M, 256), nbN = av_cdiv(p.N, 256);
         hipLaunchKernelGGL(gemm_nt_bf16_v6_kernel, dim3((unsigned)(nbM * nbN), 1, (unsigned)p.batch), dim3(V6_NT), V6_LDS, st, p, nbM, nbN, fl);
+        note_launch(AV_GEMM_KERNEL_V6, p, fl, 256, false, false, false, 0, 256, nbM, nbN, nbM * nbN, (unsigned)(nbM * nbN), (unsigned)p.batch);
         AV_LAUNCH_CHECK();
         return AV_OK;
     }
@@ -2140,6 +2157,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
                     attr = true;
                 }
                 hipLaunchKernelGGL(kern, dim3((unsigned)G, 1, (unsigned)p.batch), dim3(V4_NT), V4_LDS, st, p, nbM, nbN4, fl, nfull, best_bm);
+                note_launch(AV_GEMM_KERNEL_V7, p, fl, V4_BN, false, false, false, best_bm <= 224 ? 3 : 4, best_bm, nbM, nbN4, nfull, (unsigned)G, (unsigned)p.batch);
             };
             const bool nm3 = best_bm <= 224;                 // tiles of <= 224 rows: three m-tiles per wavefront in the second A half
             if (p.out_dtype == AV_F32) { if (nm3) go(gemm_nt_bf16_v7_kernel<AV_ACT_NONE, AV_F32, true, 3>); else go(gemm_nt_bf16_v7_kernel<AV_ACT_NONE, AV_F32, true, 4>); }
@@ -2165,6 +2183,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
             const int nfull = p.batch == 1 ? best_full : ntile;
             const unsigned nblocks = (unsigned)(nfull + 4 * (ntile - nfull));
             hipLaunchKernelGGL(gemm_nt_bf16_v4_kernel<false>, dim3(nblocks, 1, (unsigned)p.batch), dim3(V4_NT), V4_LDS, st, p, nbM, nbN4, fl, nfull, best_bm);
+            note_launch(AV_GEMM_KERNEL_V4, p, fl, V4_BN, false, false, false, 0, best_bm, nbM, nbN4, nfull, nblocks, (unsigned)p.batch);
             AV_LAUNCH_CHECK();
             return AV_OK;
         }
@@ -2180,6 +2199,7 @@ int av_gemm_fast_try(const av_gemm_args& p, hipStream_t st) {
         }
         const int nbM = av_cdiv(p.M, V2_BM), nbN = av_cdiv(p.N, V2_BN);
         hipLaunchKernelGGL(gemm_nt_bf16_v2_kernel, dim3((unsigned)(nbM * (long long)nbN), 1, (unsigned)p.batch), dim3(V2_NT), V2_LDS, st, p, nbM, nbN, fl);
+        note_launch(AV_GEMM_KERNEL_V2, p, fl, V2_BN, false, false, false, 0, V2_BM, nbM, nbN, nbM * nbN, (unsigned)(nbM * (long long)nbN), (unsigned)p.batch);
         AV_LAUNCH_CHECK();
         return AV_OK;
     }
