@@ -81,13 +81,8 @@ def _host_align(lp: np.ndarray, target, Tb: int, Lb: int, Lmax: int, blank: int)
 def _lengths(t, name: str, B: int, default: int, device) -> torch.Tensor:
     if t is None:
         return torch.full((B,), default, dtype=torch.long, device=device)
-    if not isinstance(t, torch.Tensor):
-        t = torch.as_tensor(t, dtype=torch.long)
-    if t.dim() != 1 or t.numel() != B:
-        raise ValueError(f"forced_align: {name} must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
-    if t.dtype.is_floating_point or t.dtype == torch.bool:
-        raise TypeError(f"forced_align: {name} must be an integer tensor, got {t.dtype}")
-    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()
+    from .ops import _ctc_lengths
+    return _ctc_lengths("forced_align", name, t, B, device)
 
 
 def forced_align(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths=None, target_lengths=None, blank: int = 0,

@@ -8,7 +8,7 @@ __global__ __launch_bounds__(256) void context_bias_count_kernel(const int* __re
                                                                  int* __restrict__ out, int B, int Lmax, BiasTables t, int V, int blank) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    const int len = clamped_length(lens, b, Lmax);
+    const int len = ctc_clamp_len(lens, b, Lmax);
     const int* row = ids + (long long)b * Lmax;
     int2* o = (int2*)out + (long long)b * Lmax;
     int node = 0, k = 0;

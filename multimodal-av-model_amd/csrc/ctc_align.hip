@@ -23,7 +23,7 @@
 //               state is visited and its run is contiguous); then one thread per target position adds its emissions in frame order.
 // Determinism: no atomics, every sum has a fixed order.  Out-of-range data cannot cause out-of-bounds accesses: T_b is clamped to [0, T],
 // L_b to [0, Lmax], a bad label ends the item before any emission is gathered, and the walk clamps its state at 0.
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -31,9 +31,6 @@ constexpr int ALN_TCHUNK = 16;                    // frames per staged batch of 
 constexpr int ALN_BT_ROWS = 16;                   // chunk rows of move words staged per back-trace batch (the emission buffer, reused)
 constexpr int ALN_MAXTRIP = 4;                    // trips of the state loop at 256 threads: S_max <= 1024 (the LDS limit allows 818)
 constexpr int ALN_MAXT = 4096;
-constexpr long long ALN_LDS_LIMIT = 64 * 1024;
-
-__device__ __forceinline__ int aln_clamp_len(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
 __host__ __device__ __forceinline__ long long aln_chunks(int T) { return (T + ALN_TCHUNK - 1) / ALN_TCHUNK; }
 
@@ -56,8 +53,8 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
     const int tid = threadIdx.x, nt = blockDim.x;
     const int b = blockIdx.x;
     const int Lmax = (S_max - 1) / 2;
-    const int Tb = aln_clamp_len(input_lengths[b], T);
-    const int Lb = aln_clamp_len(target_lengths[b], Lmax);
+    const int Tb = ctc_clamp_len(input_lengths[b], T);
+    const int Lb = ctc_clamp_len(target_lengths[b], Lmax);
     const int S = 2 * Lb + 1;
     if (tid == 0) bad = 0;
     __syncthreads();
@@ -208,7 +205,7 @@ long long aln_lds_bytes(int T, int S_max) {
 extern "C" int av_ctc_align_workspace_bytes(int B, int T, int S_max, long long* bytes) {
     AV_CHECK(bytes, "av_ctc_align_workspace_bytes: null pointer");
     AV_CHECK(B >= 1 && T >= 1 && T <= ALN_MAXT, "av_ctc_align_workspace_bytes: bad shape B=%d T=%d (B >= 1, 1 <= T <= %d)", B, T, ALN_MAXT);
-    AV_CHECK(S_max >= 1 && (S_max & 1), "av_ctc_align_workspace_bytes: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", S_max);
+    if (int rc = ctc_check_smax("av_ctc_align_workspace_bytes", S_max)) return rc;
     *bytes = (long long)B * aln_chunks(T) * S_max * (long long)sizeof(unsigned);
     return AV_OK;
 }
@@ -219,17 +216,15 @@ extern "C" int av_ctc_align(const float* log_probs, long long stride_b, long lon
                             long long workspace_bytes, void* stream) {
     AV_CHECK(log_probs && targets && input_lengths && target_lengths && out_state && out_score && workspace, "av_ctc_align: null pointer");
     AV_CHECK(B >= 1 && T >= 1 && T <= ALN_MAXT && V >= 1, "av_ctc_align: bad shape B=%d T=%d V=%d (1 <= T <= %d)", B, T, V, ALN_MAXT);
-    AV_CHECK(blank >= 0 && blank < V, "av_ctc_align: blank %d outside [0, %d)", blank, V);
-    AV_CHECK(S_max >= 1 && (S_max & 1), "av_ctc_align: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", S_max);
+    if (int rc = ctc_check_blank("av_ctc_align", blank, V)) return rc;
+    if (int rc = ctc_check_smax("av_ctc_align", S_max)) return rc;
     AV_CHECK(S_max == 1 || (out_span && out_token_score), "av_ctc_align: null pointer (out_span / out_token_score with Lmax = %d)",
              (S_max - 1) / 2);
     AV_CHECK(target_ld >= (S_max - 1) / 2, "av_ctc_align: target_ld %lld < Lmax %d", target_ld, (S_max - 1) / 2);
-    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b >= (long long)T * stride_t) ||
-                                                 (stride_b >= V && stride_t >= (long long)B * stride_b)),
-             "av_ctc_align: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", stride_b, stride_t, B, T, V);
+    if (int rc = ctc_check_rows("av_ctc_align", stride_b, stride_t, B, T, V, true, "btBT")) return rc;
     const long long lds = aln_lds_bytes(T, S_max);
-    AV_CHECK(lds <= ALN_LDS_LIMIT && S_max <= 256 * ALN_MAXTRIP, "av_ctc_align: S_max %d at T %d needs %lld bytes of LDS (limit %lld)", S_max, T,
-             lds, ALN_LDS_LIMIT);
+    AV_CHECK(lds <= CTC_LDS_LIMIT && S_max <= 256 * ALN_MAXTRIP, "av_ctc_align: S_max %d at T %d needs %lld bytes of LDS (limit %lld)", S_max, T,
+             lds, CTC_LDS_LIMIT);
     const long long need = (long long)B * aln_chunks(T) * S_max * (long long)sizeof(unsigned);
     AV_CHECK(workspace_bytes >= need, "av_ctc_align: workspace of %lld bytes is too small, %lld needed", workspace_bytes, need);
     AV_CHECK((uintptr_t)workspace % sizeof(unsigned) == 0, "av_ctc_align: workspace must be 4-byte aligned");

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const float* __rest
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
     if (t >= T) return;
-    if (t >= clamped_length(lengths, b, T)) return;
+    if (t >= ctc_clamp_len(lengths, b, T)) return;
     const float* row = lp + (long long)b * stride_b + (long long)t * stride_t;
     const bool in_regs = V <= 64 * ROW_REGS;
     float r[ROW_REGS];
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
     if constexpr (BIAS) has_lm = f.lm.order > 0;
 
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int Tb = clamped_length(lengths, b, T);
+    const int Tb = ctc_clamp_len(lengths, b, T);
     const float* base = lp + (long long)b * stride_b;
     const long long tb = (long long)b * T;
     const int C = K + 1;                             // candidates per live entry
@@ -329,13 +329,13 @@ static int beam_check(const char* who, const float* log_probs, void* workspace, 
     AV_CHECK(log_probs && workspace, "%s: null pointer", who);
     AV_CHECK(B >= 0 && B <= 65535 && T >= 1 && T <= MAXT && V >= 2, "%s: bad shape B=%d T=%d V=%d (B <= 65535, 1 <= T <= %d, V >= 2)", who, B,
              T, V, MAXT);
-    AV_CHECK(blank >= 0 && blank < V, "%s: blank %d outside [0, %d)", who, blank, V);
+    if (int rc = ctc_check_blank(who, blank, V)) return rc;
     AV_CHECK(beam_width >= 1 && beam_width <= MAXW, "%s: beam_width %d outside [1, %d]", who, beam_width, MAXW);
     return AV_OK;
 }
 static int beam_check_memory(const char* who, bool rows, long long stride_b, long long stride_t, long long workspace_bytes, int B, int T,
                              int V, int beam_width, int wf) {
-    AV_CHECK(!rows || (stride_t >= V && stride_b >= (long long)T * stride_t), "%s: strides (%lld, %lld) overlap rows of [%d][%d][%d]", who,
+    AV_CHECK(!rows || ctc_rows_fit(stride_b, stride_t, T, V), "%s: strides (%lld, %lld) overlap rows of [%d][%d][%d]", who,
              stride_b, stride_t, B, T, V);
     const long long need = beam_workspace(B, T, beam_width, wf).total;
     AV_CHECK(workspace_bytes >= need, "%s: workspace of %lld bytes is too small, %lld needed", who, workspace_bytes, need);

@@ -1,8 +1,8 @@
 // The small parts of the CTC prefix beam search (ctc_beam.hip) that are not the search itself: the limits, the workspace layout, the
-// length clamp, the log-sum, the order-preserving key of a score, the 64-bit mixer (also the n-gram table's hash, ngram_lm.h), the content
+// log-sum, the order-preserving key of a score, the 64-bit mixer (also the n-gram table's hash, ngram_lm.h), the content
 // hash of a prefix, the workgroup scan and the radix select.
 #pragma once
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -22,11 +22,6 @@ static BeamWorkspace beam_workspace(long long B, long long T, long long W, long 
     const long long top = B * T * (wf + 1) * 4, arena = B * T * W * 4;
     w.topv = 0; w.topt = top; w.apar = 2 * top; w.atok = 2 * top + arena; w.total = 2 * top + 2 * B * T * (W > wf ? W : wf) * 4;
     return w;
-}
-
-// frames (or tokens) of item b that are consumed: lengths[b] clamped to [0, T], T without lengths
-__device__ __forceinline__ int clamped_length(const long long* lengths, int b, int T) {
-    return lengths ? (int)min(max(lengths[b], 0ll), (long long)T) : T;
 }
 
 __device__ __forceinline__ float logaddexp_f(float a, float b) {

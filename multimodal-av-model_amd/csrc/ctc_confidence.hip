@@ -18,19 +18,13 @@
 //   ctc_greedy_timed_kernel   ctc_greedy_kernel's structure (csrc/decode.hip), one workgroup per utterance: a wavefront per frame leaves argmax and
 //                             confidence in LDS, one lane collapses the path into runs, then every thread writes one output position
 // Out-of-range data cannot cause out-of-bounds accesses: T_b is clamped to [0, T], spans are clipped to [0, T_b).
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
 constexpr int CONF_MAXT = 4096;
 constexpr int CONF_REGS = 32;                     // row elements a lane keeps in registers: 64 lanes x 32 = rows of up to 2048
 constexpr int CONF_ROWS = 4;                      // frame rows (wavefronts) per workgroup
-
-__device__ __forceinline__ int conf_len(const long long* lengths, int b, int T) {
-    if (!lengths) return T;
-    const long long v = lengths[b];
-    return v < 0 ? 0 : (v > T ? T : (int)v);
-}
 
 // first maximal index, as torch.argmax and ctc_greedy_kernel: a NaN never wins
 __device__ __forceinline__ void conf_take(float x, int v, float& best, int& bi) {
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(64 * CONF_ROWS) void ctc_frame_conf_kernel(const fl
     if (i >= (long long)B * T) return;
     const int b = (int)(i / T), t = (int)(i % T);
     float c = 0.f;
-    if (t < conf_len(lengths, b, T)) {
+    if (t < ctc_clamp_len(lengths, b, T)) {
         int arg;
         c = conf_row<VEC, METHOD>(lp + (long long)b * stride_b + (long long)t * stride_t, V, lane, alpha, arg);
     }
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(256) void ctc_span_conf_kernel(const float* __restr
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)B * L) return;
     const int b = (int)(i / L);
-    const int f = max(spans[2 * i], 0), e = min(spans[2 * i + 1], conf_len(lengths, b, T));
+    const int f = max(spans[2 * i], 0), e = min(spans[2 * i + 1], ctc_clamp_len(lengths, b, T));
     token_conf[i] = f < e ? conf_aggregate(conf + (long long)b * T, f, e, aggregation) : 0.f;
 }
 
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(256) void ctc_greedy_timed_kernel(const float* __re
     __shared__ unsigned short first[CONF_MAXT], end[CONF_MAXT];      // the run of equal argmax frames behind emitted id j
     __shared__ int count;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int Tb = conf_len(lengths, b, T);
+    const int Tb = ctc_clamp_len(lengths, b, T);
     const float* base = lp + (long long)b * stride_b;
     for (int t = w; t < Tb; t += 4) {
         int arg;
@@ -248,15 +242,7 @@ int conf_check_rows(const char* who, const float* lp, long long stride_b, long l
         AV_CHECK(fabsf(alpha - 1.f) >= 1.f / 64.f, "%s: tsallis alpha %g is within 1/64 of 1, where the law loses its digits: use the entropy "
                  "method, its alpha -> 1 limit", who, (double)alpha);
     }
-    // [B][T][V]: stride_b >= T stride_t, or [T][B][V]: stride_t >= B stride_b - as quotients, which no stride can overflow
-    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b / T >= stride_t) ||
-                                                 (stride_b >= V && stride_t / (B > 0 ? B : 1) >= stride_b)),
-             "%s: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", who, stride_b, stride_t, B, T, V);
-    return AV_OK;
-}
-
-bool conf_vec_ok(const float* lp, long long stride_b, long long stride_t, int V) {
-    return (uintptr_t)lp % 16 == 0 && stride_b % 4 == 0 && stride_t % 4 == 0 && V % 4 == 0;
+    return ctc_check_rows(who, stride_b, stride_t, B, T, V, true, "btBT");
 }
 
 bool conf_agg_ok(int a) { return a == AV_AGG_MEAN || a == AV_AGG_MIN || a == AV_AGG_PROD; }
@@ -282,7 +268,7 @@ extern "C" int av_ctc_frame_conf(const float* log_probs, long long stride_b, lon
     AV_CHECK(log_probs && conf, "av_ctc_frame_conf: null pointer");
     if (int rc = conf_check_rows("av_ctc_frame_conf", log_probs, stride_b, stride_t, B, T, V, method, alpha)) return rc;
     if (B == 0) return AV_OK;
-    const bool vec = conf_vec_ok(log_probs, stride_b, stride_t, V);
+    const bool vec = ctc_vec_ok(log_probs, nullptr, stride_b, stride_t, V);
     const unsigned grid = (unsigned)av_cdiv((long long)B * T, CONF_ROWS);
 #define CONF_FRAME(VEC_, METHOD_, ...)                                                                                                     \
     hipLaunchKernelGGL((ctc_frame_conf_kernel<VEC_, METHOD_>), dim3(grid), dim3(64 * CONF_ROWS), 0, (hipStream_t)stream, __VA_ARGS__)
@@ -310,10 +296,10 @@ extern "C" int av_ctc_greedy_timed(const float* log_probs, long long stride_b, l
                                    float* token_conf, float* frame_conf, void* stream) {
     AV_CHECK(log_probs && out_ids && out_len && out_span && token_conf && frame_conf, "av_ctc_greedy_timed: null pointer");
     if (int rc = conf_check_rows("av_ctc_greedy_timed", log_probs, stride_b, stride_t, B, T, V, method, alpha)) return rc;
-    AV_CHECK(blank >= 0 && blank < V, "av_ctc_greedy_timed: blank %d outside [0, %d)", blank, V);
+    if (int rc = ctc_check_blank("av_ctc_greedy_timed", blank, V)) return rc;
     AV_CHECK(conf_agg_ok(aggregation), "av_ctc_greedy_timed: unknown aggregation %d (0 mean, 1 min, 2 prod)", aggregation);
     if (B == 0) return AV_OK;
-    const bool vec = conf_vec_ok(log_probs, stride_b, stride_t, V);
+    const bool vec = ctc_vec_ok(log_probs, nullptr, stride_b, stride_t, V);
 #define CONF_GREEDY(VEC_, METHOD_, ...)                                                                                                    \
     hipLaunchKernelGGL((ctc_greedy_timed_kernel<VEC_, METHOD_>), dim3(B), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
     CONF_DISPATCH(CONF_GREEDY, vec, method, log_probs, stride_b, stride_t, lengths, T, V, blank, alpha, aggregation, out_ids, out_len, out_span,

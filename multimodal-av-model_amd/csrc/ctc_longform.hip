@@ -16,7 +16,7 @@
 //                              writes the segment's length
 // Out-of-range data cannot cause out-of-bounds accesses: a table index outside [0, R) counts as no source, cuts are clamped to [0, F] and a
 // segment's length to [0, segment].
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -156,15 +156,6 @@ __global__ __launch_bounds__(64 * LF_ROWS) void ctc_segment_gather_kernel(const 
     }
 }
 
-// rows [S][n][V] behind (stride_s, stride_r): contiguous rows that do not overlap - as quotients, which no stride can overflow
-bool lf_strides_ok(int S, long long stride_s, long long stride_r, long long n, int V) {
-    return stride_r >= V && (S == 1 || (stride_s > 0 && stride_s / n >= stride_r));
-}
-
-bool lf_vec_ok(const float* in, long long stride_s, long long stride_r, const float* out, int V) {
-    return (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && stride_s % 4 == 0 && stride_r % 4 == 0 && V % 4 == 0;
-}
-
 long long lf_grid(long long rows) { return (rows + LF_ROWS - 1) / LF_ROWS; }
 
 }  // namespace
@@ -175,11 +166,10 @@ extern "C" int av_ctc_stitch(const float* windows, long long stride_s, long long
     if (S == 0) return AV_OK;
     AV_CHECK(windows && src_row && src_weight && out, "av_ctc_stitch: null pointer");
     if (S == 1) stride_s = 0;                      // never multiplied by anything but 0
-    AV_CHECK(lf_strides_ok(S, stride_s, stride_r, R, V),
-             "av_ctc_stitch: strides (s %lld, r %lld) do not cover [S=%d][R=%d][V=%d] rows", stride_s, stride_r, S, R, V);
+    if (int rc = ctc_check_rows("av_ctc_stitch", stride_s, stride_r, S, R, V, false, "srSR")) return rc;
     const long long grid = lf_grid((long long)S * F);
     AV_CHECK(grid <= 0x7fffffffLL, "av_ctc_stitch: S * F = %lld rows exceed one launch", (long long)S * F);
-    if (lf_vec_ok(windows, stride_s, stride_r, out, V))
+    if (ctc_vec_ok(windows, out, stride_s, stride_r, V))
         hipLaunchKernelGGL(ctc_stitch_kernel<true>, dim3((unsigned)grid), dim3(64 * LF_ROWS), 0, (hipStream_t)stream, windows, stride_s, stride_r,
                            src_row, src_weight, S, R, F, V, out);
     else
@@ -192,15 +182,14 @@ extern "C" int av_ctc_stitch(const float* windows, long long stride_s, long long
 extern "C" int av_ctc_cut_points(const float* log_probs, long long stride_s, long long stride_t, int S, int F, int V, int blank, int segment,
                                  int radius, int* cuts, void* stream) {
     AV_CHECK(S >= 0 && F >= 1 && V >= 2, "av_ctc_cut_points: bad shape S=%d F=%d V=%d (S >= 0, F >= 1, V >= 2)", S, F, V);
-    AV_CHECK(blank >= 0 && blank < V, "av_ctc_cut_points: blank %d outside [0, %d)", blank, V);
+    if (int rc = ctc_check_blank("av_ctc_cut_points", blank, V)) return rc;
     AV_CHECK(radius >= 0 && segment >= 1 && segment <= AV_LONGFORM_MAX_SEGMENT && (long long)segment - 2LL * radius >= 2LL * radius + 1,
              "av_ctc_cut_points: need radius >= 0, segment <= %d and segment - 2 radius >= 2 radius + 1, got segment=%d radius=%d",
              AV_LONGFORM_MAX_SEGMENT, segment, radius);
     if (S == 0) return AV_OK;
     AV_CHECK(log_probs && cuts, "av_ctc_cut_points: null pointer");
     if (S == 1) stride_s = 0;
-    AV_CHECK(lf_strides_ok(S, stride_s, stride_t, F, V),
-             "av_ctc_cut_points: strides (s %lld, t %lld) do not cover [S=%d][F=%d][V=%d] rows", stride_s, stride_t, S, F, V);
+    if (int rc = ctc_check_rows("av_ctc_cut_points", stride_s, stride_t, S, F, V, false, "stSF")) return rc;
     const int N = segment - 2 * radius;
     const int nb = F - 1 - radius >= 0 ? (F - 1 - radius) / N : 0;
     const long long grid = lf_grid((long long)S * (nb + 2));
@@ -220,12 +209,11 @@ extern "C" int av_ctc_segment_gather(const float* log_probs, long long stride_s,
     if (S == 0) return AV_OK;
     AV_CHECK(log_probs && cuts && seg_log_probs && seg_lengths, "av_ctc_segment_gather: null pointer");
     if (S == 1) stride_s = 0;
-    AV_CHECK(lf_strides_ok(S, stride_s, stride_t, F, V),
-             "av_ctc_segment_gather: strides (s %lld, t %lld) do not cover [S=%d][F=%d][V=%d] rows", stride_s, stride_t, S, F, V);
+    if (int rc = ctc_check_rows("av_ctc_segment_gather", stride_s, stride_t, S, F, V, false, "stSF")) return rc;
     const long long grid = lf_grid((long long)S * (nb + 1) * segment);
     AV_CHECK(grid <= 0x7fffffffLL, "av_ctc_segment_gather: S * (nb + 1) * segment = %lld rows exceed one launch",
              (long long)S * (nb + 1) * segment);
-    if (lf_vec_ok(log_probs, stride_s, stride_t, seg_log_probs, V))
+    if (ctc_vec_ok(log_probs, seg_log_probs, stride_s, stride_t, V))
         hipLaunchKernelGGL(ctc_segment_gather_kernel<true>, dim3((unsigned)grid), dim3(64 * LF_ROWS), 0, (hipStream_t)stream, log_probs, stride_s,
                            stride_t, cuts, S, F, V, nb, segment, seg_log_probs, seg_lengths);
     else

@@ -26,14 +26,12 @@
 //                          label chains of all N hypotheses are built once per workgroup, g_n occ_n is accumulated into the LDS row in
 //                          hypothesis order (each class has one owner lane per hypothesis: no atomics), the log-prob row is read once and
 //                          grad = G_b exp(lp) - sum_n g_n occ_n, G_b = sum_n g_n over the items that are not out, is written once.
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
 constexpr int CTC_TCHUNK = 16;       // frames of gathered emissions staged per batch of loads (forward)
 constexpr int CTC_BWD_ROWS = 4;      // [b, t] rows per wavefront (backward): the label chain is built once per workgroup
-
-__device__ __forceinline__ int ctc_clamp_len(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
 // log(exp(a) + exp(b) + exp(c)) in torch's order (aten/native/LossCTC.cpp): the maximum is taken out, an all -inf triple gives -inf
 __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
@@ -389,29 +387,63 @@ __global__ __launch_bounds__(256) void ctc_nbest_grad_kernel(const float* __rest
     }
 }
 
-constexpr long long CTC_LDS_LIMIT = 64 * 1024;
+// The argument law of the four entry points.  The single-item pair is N = 1 with target_ld in the role of hyp_ld_b (nbest = false: it is
+// reported under that name).  B_max: the gradient kernels put B in grid y (65535) and the n-best lattice launches 2 B N workgroups in x
+// (B N <= 2^30); the single-item lattice launches 2 B in x and has no limit of its own (B_max = 0).
+int ctc_loss_check(const char* fn, bool nbest, int B_max, long long stride_b, long long stride_t, long long ld_b, long long ld_n, int B, int N,
+                   int T, int V, int S_max, int blank) {
+    AV_CHECK(N >= 1 && N <= 64, "%s: N = %d hypotheses per utterance outside [1, 64]", fn, N);
+    const bool shape = B >= 1 && (!B_max || B <= B_max) && T >= 1 && V >= 1;
+    if (!B_max) AV_CHECK(shape, "%s: bad shape B=%d T=%d V=%d", fn, B, T, V);
+    AV_CHECK(shape, nbest ? "%s: bad shape B=%d T=%d V=%d (1 <= B <= %d: the grid limit)" : "%s: bad shape B=%d T=%d V=%d (B <= %d)", fn, B, T, V,
+             B_max);
+    if (int rc = ctc_check_blank(fn, blank, V)) return rc;
+    if (int rc = ctc_check_smax(fn, S_max)) return rc;
+    const int Lmax = (S_max - 1) / 2;
+    if (nbest) {
+        AV_CHECK(ld_n >= Lmax, "%s: hyp_ld_n %lld < Lmax %d", fn, ld_n, Lmax);
+        AV_CHECK(ld_b >= (long long)(N - 1) * ld_n + Lmax, "%s: hyp_ld_b %lld does not cover N = %d rows of hyp_ld_n %lld", fn, ld_b, N, ld_n);
+    } else {
+        AV_CHECK(ld_b >= Lmax, "%s: target_ld %lld < Lmax %d", fn, ld_b, Lmax);
+    }
+    return ctc_check_rows(fn, stride_b, stride_t, B, T, V, true, "btBT");
+}
+
+// the lattice launch: two lattice rows, CTC_TCHUNK rows of emissions, lab[] and skip[]; one thread per state, 256 at the most
+int ctc_lattice_geometry(const char* fn, int S_max, long long* lds, int* threads) {
+    *lds = ((long long)(2 + CTC_TCHUNK) * S_max) * sizeof(float) + 2LL * S_max * sizeof(int);
+    AV_CHECK(*lds <= CTC_LDS_LIMIT, "%s: S_max %d needs %lld bytes of LDS (limit %lld)", fn, S_max, *lds, CTC_LDS_LIMIT);
+    *threads = S_max >= 256 ? 256 : (S_max + 63) / 64 * 64;
+    return AV_OK;
+}
+
+// the gradient launch: W wavefronts (= rows in flight) per workgroup, as many of 4, 2, 1 as the LDS allows beside the workgroup's
+// label_ints ints; every wavefront holds V + S_max floats and walks CTC_BWD_ROWS rows.  Returns W, 0 when not even one row fits
+int ctc_grad_geometry(int V, int S_max, long long label_ints, long long* lds, int* rows) {
+    int W = 4;
+    for (; W >= 1; W >>= 1) {
+        *lds = (long long)W * ((long long)V + S_max) * sizeof(float) + label_ints * sizeof(int);
+        if (*lds <= CTC_LDS_LIMIT) break;
+    }
+    *rows = W * CTC_BWD_ROWS;
+    return W;
+}
 
 }  // namespace
 
 extern "C" int av_ctc_loss_fwd(const float* log_probs, long long stride_b, long long stride_t, const long long* targets,
                                long long target_ld, const long long* input_lengths, const long long* target_lengths, int B, int T, int V,
                                int S_max, int blank, int zero_infinity, float* nll, float* log_alpha, float* log_beta, void* stream) {
-    AV_CHECK(log_probs && targets && input_lengths && target_lengths && nll, "av_ctc_loss_fwd: null pointer");
-    AV_CHECK(log_alpha || !log_beta, "av_ctc_loss_fwd: log_beta without log_alpha (null pointer)");
-    AV_CHECK(B >= 1 && T >= 1 && V >= 1, "av_ctc_loss_fwd: bad shape B=%d T=%d V=%d", B, T, V);
-    AV_CHECK(blank >= 0 && blank < V, "av_ctc_loss_fwd: blank %d outside [0, %d)", blank, V);
-    AV_CHECK(S_max >= 1 && (S_max & 1), "av_ctc_loss_fwd: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", S_max);
-    AV_CHECK(target_ld >= (S_max - 1) / 2, "av_ctc_loss_fwd: target_ld %lld < Lmax %d", target_ld, (S_max - 1) / 2);
-    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b >= (long long)T * stride_t) ||
-                                                 (stride_b >= V && stride_t >= (long long)B * stride_b)),
-             "av_ctc_loss_fwd: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", stride_b, stride_t, B, T, V);
-    const long long lds = ((long long)(2 + CTC_TCHUNK) * S_max) * sizeof(float) + 2LL * S_max * sizeof(int);
-    AV_CHECK(lds <= CTC_LDS_LIMIT, "av_ctc_loss_fwd: S_max %d needs %lld bytes of LDS (limit %lld)", S_max, lds, CTC_LDS_LIMIT);
-    const int threads = S_max >= 256 ? 256 : (S_max + 63) / 64 * 64;
-    const int grid = log_beta ? 2 * B : B;
-    hipLaunchKernelGGL(ctc_lattice_kernel<false>, dim3(grid), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs, stride_b, stride_t,
-                       (const void*)targets, target_ld, 0LL, input_lengths, target_lengths, B, 1, T, V, S_max, blank, zero_infinity, nll,
-                       log_alpha, log_beta);
+    const char* fn = "av_ctc_loss_fwd";
+    AV_CHECK(log_probs && targets && input_lengths && target_lengths && nll, "%s: null pointer", fn);
+    AV_CHECK(log_alpha || !log_beta, "%s: log_beta without log_alpha (null pointer)", fn);
+    if (int rc = ctc_loss_check(fn, false, 0, stride_b, stride_t, target_ld, target_ld, B, 1, T, V, S_max, blank)) return rc;
+    long long lds;
+    int threads;
+    if (int rc = ctc_lattice_geometry(fn, S_max, &lds, &threads)) return rc;
+    hipLaunchKernelGGL(ctc_lattice_kernel<false>, dim3(log_beta ? 2 * B : B), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs,
+                       stride_b, stride_t, (const void*)targets, target_ld, 0LL, input_lengths, target_lengths, B, 1, T, V, S_max, blank,
+                       zero_infinity, nll, log_alpha, log_beta);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -420,60 +452,30 @@ extern "C" int av_ctc_loss_bwd(const float* log_probs, long long stride_b, long 
                                long long target_ld, const long long* input_lengths, const long long* target_lengths, int B, int T, int V,
                                int S_max, int blank, const float* nll, const float* log_alpha, const float* log_beta,
                                const float* grad_nll, float* grad, void* stream) {
-    AV_CHECK(log_probs && targets && input_lengths && target_lengths && nll && log_alpha && log_beta && grad_nll && grad,
-             "av_ctc_loss_bwd: null pointer");
-    AV_CHECK(B >= 1 && B <= 65535 && T >= 1 && V >= 1, "av_ctc_loss_bwd: bad shape B=%d T=%d V=%d (B <= 65535)", B, T, V);
-    AV_CHECK(blank >= 0 && blank < V, "av_ctc_loss_bwd: blank %d outside [0, %d)", blank, V);
-    AV_CHECK(S_max >= 1 && (S_max & 1), "av_ctc_loss_bwd: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", S_max);
-    AV_CHECK(target_ld >= (S_max - 1) / 2, "av_ctc_loss_bwd: target_ld %lld < Lmax %d", target_ld, (S_max - 1) / 2);
-    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b >= (long long)T * stride_t) ||
-                                                 (stride_b >= V && stride_t >= (long long)B * stride_b)),
-             "av_ctc_loss_bwd: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", stride_b, stride_t, B, T, V);
-    const int Lmax = (S_max - 1) / 2;
-    int W = 4;                                            // wavefronts (= rows in flight) per workgroup: as many as the LDS rows allow
-    long long lds = 0;
-    for (; W >= 1; W >>= 1) {
-        lds = (long long)W * ((long long)V + S_max) * sizeof(float) + 3LL * Lmax * sizeof(int);
-        if (lds <= CTC_LDS_LIMIT) break;
-    }
-    AV_CHECK(W >= 1, "av_ctc_loss_bwd: V %d + S_max %d floats exceed the LDS row (limit %lld bytes)", V, S_max, CTC_LDS_LIMIT);
-    // 16-byte loads / stores need every row start on a 16-byte boundary (LDS rows: V % 4 == 0 keeps occ rows aligned)
-    const int vec = (V % 4 == 0) && (stride_b % 4 == 0) && (stride_t % 4 == 0) && ((uintptr_t)log_probs % 16 == 0) && ((uintptr_t)grad % 16 == 0);
-    const int rows = W * CTC_BWD_ROWS;
+    const char* fn = "av_ctc_loss_bwd";
+    AV_CHECK(log_probs && targets && input_lengths && target_lengths && nll && log_alpha && log_beta && grad_nll && grad, "%s: null pointer", fn);
+    if (int rc = ctc_loss_check(fn, false, 65535, stride_b, stride_t, target_ld, target_ld, B, 1, T, V, S_max, blank)) return rc;
+    int rows;
+    long long lds;
+    const int W = ctc_grad_geometry(V, S_max, 3LL * ((S_max - 1) / 2), &lds, &rows);
+    AV_CHECK(W >= 1, "%s: V %d + S_max %d floats exceed the LDS row (limit %lld bytes)", fn, V, S_max, CTC_LDS_LIMIT);
     hipLaunchKernelGGL(ctc_grad_kernel, dim3((T + rows - 1) / rows, B), dim3(64 * W), (size_t)lds, (hipStream_t)stream, log_probs, stride_b,
                        stride_t, targets, target_ld, input_lengths, target_lengths, T, V, S_max, blank, nll, log_alpha, log_beta, grad_nll,
-                       grad, vec);
+                       grad, (int)ctc_vec_ok(log_probs, grad, stride_b, stride_t, V));
     AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-// the argument law both n-best entry points share; grid limits: the lattice launches 2 B N workgroups in x (B N <= 2^30), the gradient
-// kernel puts B in grid y (B <= 65535)
-static int ctc_nbest_check(const char* fn, long long stride_b, long long stride_t, long long hyp_ld_b, long long hyp_ld_n, int B, int N, int T,
-                           int V, int S_max, int blank) {
-    AV_CHECK(N >= 1 && N <= 64, "%s: N = %d hypotheses per utterance outside [1, 64]", fn, N);
-    AV_CHECK(B >= 1 && B <= 65535 && T >= 1 && V >= 1, "%s: bad shape B=%d T=%d V=%d (1 <= B <= 65535: the grid limit)", fn, B, T, V);
-    AV_CHECK(blank >= 0 && blank < V, "%s: blank %d outside [0, %d)", fn, blank, V);
-    AV_CHECK(S_max >= 1 && (S_max & 1), "%s: S_max = 2 Lmax + 1 must be odd and >= 1, got %d", fn, S_max);
-    const int Lmax = (S_max - 1) / 2;
-    AV_CHECK(hyp_ld_n >= Lmax, "%s: hyp_ld_n %lld < Lmax %d", fn, hyp_ld_n, Lmax);
-    AV_CHECK(hyp_ld_b >= (long long)(N - 1) * hyp_ld_n + Lmax, "%s: hyp_ld_b %lld does not cover N = %d rows of hyp_ld_n %lld", fn, hyp_ld_b, N,
-             hyp_ld_n);
-    AV_CHECK(stride_b >= 0 && stride_t >= 0 && ((stride_t >= V && stride_b >= (long long)T * stride_t) ||
-                                                 (stride_b >= V && stride_t >= (long long)B * stride_b)),
-             "%s: strides (b %lld, t %lld) do not cover [B=%d][T=%d][V=%d] rows", fn, stride_b, stride_t, B, T, V);
     return AV_OK;
 }
 
 extern "C" int av_ctc_nbest_fwd(const float* log_probs, long long stride_b, long long stride_t, const int* hyp_ids, long long hyp_ld_b,
                                 long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V,
                                 int S_max, int blank, float* nll, float* log_alpha, float* log_beta, void* stream) {
-    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll, "av_ctc_nbest_fwd: null pointer");
-    AV_CHECK(log_alpha || !log_beta, "av_ctc_nbest_fwd: log_beta without log_alpha (null pointer)");
-    if (int st = ctc_nbest_check("av_ctc_nbest_fwd", stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return st;
-    const long long lds = ((long long)(2 + CTC_TCHUNK) * S_max) * sizeof(float) + 2LL * S_max * sizeof(int);
-    AV_CHECK(lds <= CTC_LDS_LIMIT, "av_ctc_nbest_fwd: S_max %d needs %lld bytes of LDS (limit %lld)", S_max, lds, CTC_LDS_LIMIT);
-    const int threads = S_max >= 256 ? 256 : (S_max + 63) / 64 * 64;
+    const char* fn = "av_ctc_nbest_fwd";
+    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll, "%s: null pointer", fn);
+    AV_CHECK(log_alpha || !log_beta, "%s: log_beta without log_alpha (null pointer)", fn);
+    if (int rc = ctc_loss_check(fn, true, 65535, stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return rc;
+    long long lds;
+    int threads;
+    if (int rc = ctc_lattice_geometry(fn, S_max, &lds, &threads)) return rc;
     const int items = B * N;                              // <= 65535 * 64
     hipLaunchKernelGGL(ctc_lattice_kernel<true>, dim3(log_beta ? 2 * items : items), dim3(threads), (size_t)lds, (hipStream_t)stream, log_probs,
                        stride_b, stride_t, (const void*)hyp_ids, hyp_ld_b, hyp_ld_n, input_lengths, hyp_lens, items, N, T, V, S_max, blank, 0,
@@ -486,23 +488,18 @@ extern "C" int av_ctc_nbest_bwd(const float* log_probs, long long stride_b, long
                                 long long hyp_ld_n, const long long* hyp_lens, const long long* input_lengths, int B, int N, int T, int V,
                                 int S_max, int blank, const float* nll, const float* log_alpha, const float* log_beta, const float* grad_nll,
                                 float* grad, void* stream) {
-    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll && log_alpha && log_beta && grad_nll && grad,
-             "av_ctc_nbest_bwd: null pointer");
-    if (int st = ctc_nbest_check("av_ctc_nbest_bwd", stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return st;
-    const int Lmax = (S_max - 1) / 2;
-    int W = 4;                                            // wavefronts (= rows in flight) per workgroup: as many as the LDS rows allow
-    long long lds = 0;
-    for (; W >= 1; W >>= 1) {
-        lds = (long long)W * ((long long)V + S_max) * sizeof(float) + 3LL * N * Lmax * sizeof(int) + 3LL * N * sizeof(int);
-        if (lds <= CTC_LDS_LIMIT) break;
-    }
-    AV_CHECK(W >= 1, "av_ctc_nbest_bwd: V %d + S_max %d floats and 3 N Lmax = %lld label ints exceed the LDS (limit %lld bytes)", V, S_max,
-             3LL * N * Lmax, CTC_LDS_LIMIT);
-    const int vec = (V % 4 == 0) && (stride_b % 4 == 0) && (stride_t % 4 == 0) && ((uintptr_t)log_probs % 16 == 0) && ((uintptr_t)grad % 16 == 0);
-    const int rows = W * CTC_BWD_ROWS;
+    const char* fn = "av_ctc_nbest_bwd";
+    AV_CHECK(log_probs && hyp_ids && hyp_lens && input_lengths && nll && log_alpha && log_beta && grad_nll && grad, "%s: null pointer", fn);
+    if (int rc = ctc_loss_check(fn, true, 65535, stride_b, stride_t, hyp_ld_b, hyp_ld_n, B, N, T, V, S_max, blank)) return rc;
+    int rows;
+    long long lds;
+    const long long labels = 3LL * N * ((S_max - 1) / 2);
+    const int W = ctc_grad_geometry(V, S_max, labels + 3LL * N, &lds, &rows);
+    AV_CHECK(W >= 1, "%s: V %d + S_max %d floats and 3 N Lmax = %lld label ints exceed the LDS (limit %lld bytes)", fn, V, S_max, labels,
+             CTC_LDS_LIMIT);
     hipLaunchKernelGGL(ctc_nbest_grad_kernel, dim3((T + rows - 1) / rows, B), dim3(64 * W), (size_t)lds, (hipStream_t)stream, log_probs,
                        stride_b, stride_t, hyp_ids, hyp_ld_b, hyp_ld_n, hyp_lens, input_lengths, N, T, V, S_max, blank, nll, log_alpha, log_beta,
-                       grad_nll, grad, vec);
+                       grad_nll, grad, (int)ctc_vec_ok(log_probs, grad, stride_b, stride_t, V));
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -26,7 +26,7 @@
 //                      always in lane j % 64, so every LDS word has ONE owner lane and the row loop needs no barrier.  Per chunk of 64
 //                      columns: the diagonal neighbour by a lane shift, six shift-and-min steps for the prefix-min (DPP moves of the two
 //                      halves of a key: no LDS round trip), the last lane's value carried into the next chunk.
-#include "av_common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -38,7 +38,6 @@ constexpr long long ERC_INS = 1LL << 32;
 constexpr long long ERC_DEL = (1LL << 32) | 1LL;
 constexpr long long ERC_SUB = (1LL << 32) | (1LL << 16);
 constexpr long long ERC_INF = 1LL << 60;          // cost <= 8192 << 32: sums with it stay far from the sign bit
-constexpr long long ERC_LDS_LIMIT = 64 * 1024;
 
 // Workspace of one sequence, in ints: meta [4] | kept ids [Lt] | stripped text [Cmax] | word (start, length) [Wmax][2] | word hash [Wmax]
 struct ErcLayout {
@@ -55,8 +54,6 @@ ErcLayout erc_layout(int Lr, int Lh, int max_piece) {
     l.per = ERC_META + (long long)l.Lt + l.Cmax + 3LL * l.Wmax;
     return l;
 }
-
-__device__ __forceinline__ int erc_clamp_len(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
 // exclusive scan of (a, b) over the 256 threads of the workgroup and the totals; wt: LDS [2 * 4].  Two barriers, uniform call sites only
 __device__ __forceinline__ void erc_block_scan(int a, int b, int* wt, int& ex_a, int& ex_b, int& tot_a, int& tot_b) {
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(ERC_THREADS) void erc_expand_kernel(const int* __re
             return;
         }
     }
-    const int len = erc_clamp_len(raw, L);
+    const int len = ctc_clamp_len(raw, L);
     int base_k = 0, base_c = 0;
     for (int t0 = 0; t0 < len; t0 += ERC_THREADS) {
         const int i = t0 + tid;
@@ -322,7 +319,7 @@ extern "C" int av_error_counts(const int* ref_ids, long long ref_ld, const long 
     const int maxn = l.Lt > l.Cmax ? l.Lt : l.Cmax;                          // symbols of a hypothesis at any level
     const int cols = (maxn + 1 + 1) / 2 * 2;                                 // even: the int array behind the row stays 8-byte aligned
     const long long lds = (long long)cols * sizeof(long long) + (long long)cols * sizeof(int);
-    AV_CHECK(lds <= ERC_LDS_LIMIT, "av_error_counts: %d columns need %lld bytes of LDS (limit %lld)", cols, lds, ERC_LDS_LIMIT);
+    AV_CHECK(lds <= CTC_LDS_LIMIT, "av_error_counts: %d columns need %lld bytes of LDS (limit %lld)", cols, lds, CTC_LDS_LIMIT);
     hipLaunchKernelGGL(erc_expand_kernel, dim3(B * (N + 1)), dim3(ERC_THREADS), 0, (hipStream_t)stream, ref_ids, ref_ld, ref_lens, hyp_ids,
                        hyp_ld_b, hyp_ld_n, hyp_lens, N, Lr, Lh, ref_skip_id, hyp_skip_id, piece_offsets, piece_chars, V, max_piece, l.Lt,
                        l.Cmax, l.Wmax, l.per, (int*)workspace);

@@ -9,7 +9,7 @@ __global__ __launch_bounds__(256) void ngram_score_kernel(const int* __restrict_
     const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
     if (x >= (long long)B * Lmax) return;
     const int b = (int)(x / Lmax), i = (int)(x - (long long)b * Lmax);
-    const int len = clamped_length(lens, b, Lmax);
+    const int len = ctc_clamp_len(lens, b, Lmax);
     if (i >= len) { out[x] = 0.f; return; }
     const int* row = ids + (long long)b * Lmax;
     const int have = min(i, lm.order - 1);

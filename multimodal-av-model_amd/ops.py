@@ -557,31 +557,59 @@ def native_ctc_default() -> bool:
     return os.environ.get("AVAMD_NATIVE_CTC", "0") != "0"
 
 
-def _ctc_lengths(t, name: str, B: int, device) -> Tensor:
+def _ctc_rows(who: str, log_probs, batch_first: bool, *, max_T: Optional[int] = None, min_V: int = 1):
+    """The validated fp32 GPU block [B, T, V] (``batch_first``) or [T, B, V] of a CTC call -> (detached view with contiguous rows, B, T, V,
+    stride_b, stride_t); a view whose last dimension is not contiguous is copied.  ``max_T``: also V >= ``min_V`` and 1 <= T <= ``max_T``."""
+    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
+        raise RuntimeError(f"{who} (HIP): log_probs must be on the GPU; there is no CPU fallback (the host paths take host tensors)")
+    if log_probs.dim() != 3:
+        raise ValueError(f"{who}: log_probs must be [B, T, V] with batch_first, [T, B, V] without, got shape {tuple(log_probs.shape)}")
+    if log_probs.dtype != torch.float32:
+        raise TypeError(f"{who}: log_probs must be float32 (the CTC kernels have no low-precision operand), got {log_probs.dtype}")
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    if batch_first:
+        (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
+    else:
+        (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+    if max_T is not None and (V < min_V or not 1 <= T <= max_T):
+        raise ValueError(f"{who}: need V >= {min_V} and 1 <= T <= {max_T}, got T={T} V={V}")
+    return lp, B, T, V, sb, st
+
+
+def _ctc_lengths(who: str, name: str, t, B: int, device, optional: bool = False) -> Optional[Tensor]:
+    """An integer length vector of B items -> int64 on ``device``; a host tensor is copied without blocking."""
+    if t is None and optional:
+        return None
     if not isinstance(t, Tensor):
         t = torch.as_tensor(t, dtype=torch.long)
     if t.dim() != 1 or t.numel() != B:
-        raise ValueError(f"ctc_loss: {name} must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
+        raise ValueError(f"{who}: {name} must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
     if t.dtype.is_floating_point or t.dtype == torch.bool:
-        raise TypeError(f"ctc_loss: {name} must be an integer tensor, got {t.dtype}")
-    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()        # a host tensor is copied without blocking
+        raise TypeError(f"{who}: {name} must be an integer tensor, got {t.dtype}")
+    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()
+
+
+def _ctc_targets(targets: Tensor, B: int, device):
+    """Padded integer targets [B, Lmax] -> (int64 rows on ``device`` with a unit inner stride and a row stride >= Lmax, Lmax); Lmax = 0
+    gives one column of zeros, which the kernels never read."""
+    Lmax = targets.shape[1]
+    tg = targets.to(device=device, dtype=torch.long, non_blocking=True)
+    if Lmax == 0:
+        tg = torch.zeros((B, 1), dtype=torch.long, device=device)
+    elif tg.stride(1) != 1 or tg.stride(0) < Lmax:
+        tg = tg.contiguous()
+    return tg, Lmax
 
 
 class _CtcLossFn(torch.autograd.Function):
-    """nll [B] = av_ctc_loss_fwd; d nll / d log_probs = av_ctc_loss_bwd (torch's form: grad_nll (exp(lp) - occupancy))."""
+    """nll [B] = av_ctc_loss_fwd; d nll / d log_probs = av_ctc_loss_bwd (torch's form: grad_nll (exp(lp) - occupancy)).  ``rows`` is
+    ``_ctc_rows`` of ``log_probs``, ``tg`` the targets of ``_ctc_targets``."""
 
     @staticmethod
-    def forward(fctx, log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, batch_first):
-        lp = log_probs.detach()
-        if lp.stride(2) != 1:
-            lp = lp.contiguous()
-        if batch_first:
-            (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
-        else:
-            (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
-        Lmax = targets.shape[1]
-        tg = targets if (Lmax > 0 and targets.stride(1) == 1 and targets.stride(0) >= Lmax) else \
-            (targets.contiguous() if Lmax > 0 else torch.zeros((B, 1), dtype=torch.long, device=lp.device))
+    def forward(fctx, log_probs, rows, tg, Lmax, input_lengths, target_lengths, blank, zero_infinity, batch_first):
+        lp, B, T, V, sb, st = rows
         S_max = 2 * Lmax + 1
         need = fctx.needs_input_grad[0]
         nll = torch.empty(B, dtype=torch.float32, device=lp.device)
@@ -602,7 +630,7 @@ class _CtcLossFn(torch.autograd.Function):
         grad = torch.empty((B, T, V), dtype=torch.float32, device=lp.device)
         L.check(L.lib().av_ctc_loss_bwd(ptr(lp), sb, st, ptr(tg), tg.stride(0), ptr(il), ptr(tl), B, T, V, S_max, blank, ptr(nll), ptr(la),
                                         ptr(lb), ptr(g), ptr(grad), stream()), "av_ctc_loss_bwd")
-        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None
+        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None, None, None
 
 
 def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, reduction: str = "mean",
@@ -612,26 +640,20 @@ def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, 
     dimension is taken without a copy.  ``targets`` int64 [B, Lmax], padded (the 1-D concatenated form is not supported).  The
     lengths may live on the device (nothing is read back) or on the host (copied without blocking).  With ``zero_infinity=False`` an
     infeasible item returns +inf and its gradient is unspecified (here: zero)."""
-    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
-        raise RuntimeError("ctc_loss (HIP): log_probs must be on the GPU; there is no CPU fallback")
-    if log_probs.dim() != 3:
-        raise ValueError(f"ctc_loss: log_probs must be [T, B, V] (or [B, T, V] with batch_first), got shape {tuple(log_probs.shape)}")
-    if log_probs.dtype != torch.float32:
-        raise TypeError(f"ctc_loss: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
+    rows = _ctc_rows("ctc_loss", log_probs, batch_first)
     if reduction not in ("none", "mean", "sum"):
         raise ValueError(f"ctc_loss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
-    B = log_probs.shape[0 if batch_first else 1]
+    B, dev = rows[1], log_probs.device
     if targets.dim() != 2:
         raise NotImplementedError("ctc_loss (HIP): targets must be the padded 2-D form [B, Lmax]; 1-D concatenated targets are not supported")
     if targets.shape[0] != B:
         raise ValueError(f"ctc_loss: targets has {targets.shape[0]} rows for a batch of {B}")
     if targets.dtype.is_floating_point or targets.dtype == torch.bool:
         raise TypeError(f"ctc_loss: targets must be an integer tensor, got {targets.dtype}")
-    dev = log_probs.device
-    tg = targets.to(device=dev, dtype=torch.long, non_blocking=True)
-    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
-    tl = _ctc_lengths(target_lengths, "target_lengths", B, dev)
-    nll = _CtcLossFn.apply(log_probs, tg, il, tl, int(blank), bool(zero_infinity), bool(batch_first))
+    tg, Lmax = _ctc_targets(targets, B, dev)
+    il = _ctc_lengths("ctc_loss", "input_lengths", input_lengths, B, dev)
+    tl = _ctc_lengths("ctc_loss", "target_lengths", target_lengths, B, dev)
+    nll = _CtcLossFn.apply(log_probs, rows, tg, Lmax, il, tl, int(blank), bool(zero_infinity), bool(batch_first))
     if reduction == "none":
         return nll
     if reduction == "sum":
@@ -643,14 +665,8 @@ class _CtcNbestFn(torch.autograd.Function):
     """nll [B, N] = av_ctc_nbest_fwd; d (sum g nll) / d log_probs = av_ctc_nbest_bwd: one [B, T, V] gradient for the N hypotheses."""
 
     @staticmethod
-    def forward(fctx, log_probs, hyp_ids, hyp_lengths, input_lengths, blank, batch_first, S_max):
-        lp = log_probs.detach()
-        if lp.stride(2) != 1:
-            lp = lp.contiguous()
-        if batch_first:
-            (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
-        else:
-            (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
+    def forward(fctx, log_probs, rows, hyp_ids, hyp_lengths, input_lengths, blank, batch_first, S_max):
+        lp, B, T, V, sb, st = rows
         N, Lh = hyp_ids.shape[1], hyp_ids.shape[2]
         Lmax = (S_max - 1) // 2
         ld_n = hyp_ids.stride(1) if N > 1 else max(Lh, 1)
@@ -674,7 +690,7 @@ class _CtcNbestFn(torch.autograd.Function):
         grad = torch.empty((B, T, V), dtype=torch.float32, device=lp.device)
         L.check(L.lib().av_ctc_nbest_bwd(ptr(lp), sb, st, ptr(hi), ld_b, ld_n, ptr(hl), ptr(il), B, N, T, V, S_max, blank, ptr(nll), ptr(la),
                                          ptr(lb), ptr(g), ptr(grad), stream()), "av_ctc_nbest_bwd")
-        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None
+        return (grad if batch_first else grad.transpose(0, 1)), None, None, None, None, None, None, None
 
 
 def ctc_nbest_nll(log_probs: Tensor, hyp_ids: Tensor, hyp_lengths, input_lengths, blank: int = 0, batch_first: bool = True,
@@ -688,13 +704,8 @@ def ctc_nbest_nll(log_probs: Tensor, hyp_ids: Tensor, hyp_lengths, input_lengths
     that position never read - when its length is < 0 (absent) or > ``max_len`` (not clamped), when an id is outside [0, V) or when no path
     exists.  ``max_len`` (default Lh) sets the lattice width S_max = 2 max_len + 1 for callers who want smaller workspaces; every other
     hypothesis' nll is bit for bit ``ctc_loss(..., reduction="none", zero_infinity=False)`` of that item."""
-    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
-        raise RuntimeError("ctc_nbest_nll (HIP): log_probs must be on the GPU; there is no CPU fallback")
-    if log_probs.dim() != 3:
-        raise ValueError(f"ctc_nbest_nll: log_probs must be [B, T, V] (or [T, B, V] with batch_first=False), got shape {tuple(log_probs.shape)}")
-    if log_probs.dtype != torch.float32:
-        raise TypeError(f"ctc_nbest_nll: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
-    B = log_probs.shape[0 if batch_first else 1]
+    rows = _ctc_rows("ctc_nbest_nll", log_probs, batch_first)
+    B = rows[1]
     if not isinstance(hyp_ids, Tensor) or hyp_ids.dim() != 3 or hyp_ids.shape[0] != B:
         raise ValueError(f"ctc_nbest_nll: hyp_ids must be an integer tensor [B={B}, N, Lh], got "
                          f"{tuple(hyp_ids.shape) if isinstance(hyp_ids, Tensor) else type(hyp_ids).__name__}")
@@ -717,8 +728,8 @@ def ctc_nbest_nll(log_probs: Tensor, hyp_ids: Tensor, hyp_lengths, input_lengths
     if hyp_lengths.dtype.is_floating_point or hyp_lengths.dtype == torch.bool or hyp_lengths.numel() != B * N:
         raise ValueError(f"ctc_nbest_nll: hyp_lengths must hold [B={B}, N={N}] integer lengths, got {hyp_lengths.dtype} {tuple(hyp_lengths.shape)}")
     hl = hyp_lengths.reshape(B, N).to(device=dev, dtype=torch.long, non_blocking=True).contiguous()
-    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
-    return _CtcNbestFn.apply(log_probs, hi, hl, il, int(blank), bool(batch_first), 2 * max_len + 1)
+    il = _ctc_lengths("ctc_nbest_nll", "input_lengths", input_lengths, B, dev)
+    return _CtcNbestFn.apply(log_probs, rows, hi, hl, il, int(blank), bool(batch_first), 2 * max_len + 1)
 
 
 def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, batch_first: bool = False):
@@ -726,32 +737,15 @@ def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths,
     (``batch_first``: [B, T, V]), any view with a contiguous last dimension is taken without a copy; ``targets`` integer [B, Lmax], padded;
     lengths on the device (nothing is read back) or on the host (copied without blocking).  Returns (states int32 [B, T], spans int32
     [B, Lmax, 2], token_scores fp32 [B, Lmax], score fp32 [B]) on the device; the law and the outputs of an infeasible item: align.py."""
-    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
-        raise RuntimeError("ctc_align (HIP): log_probs must be on the GPU; there is no CPU fallback")
-    if log_probs.dim() != 3:
-        raise ValueError(f"ctc_align: log_probs must be [T, B, V] (or [B, T, V] with batch_first), got shape {tuple(log_probs.shape)}")
-    if log_probs.dtype != torch.float32:
-        raise TypeError(f"ctc_align: log_probs must be float32 (the CTC lattice has no low-precision operand), got {log_probs.dtype}")
+    lp, B, T, V, sb, st = _ctc_rows("ctc_align", log_probs, batch_first)
     if targets.dim() != 2 or targets.dtype.is_floating_point or targets.dtype == torch.bool:
         raise TypeError(f"ctc_align: targets must be an integer tensor [B, Lmax], got {targets.dtype} {tuple(targets.shape)}")
-    lp = log_probs.detach()
-    if lp.stride(2) != 1:
-        lp = lp.contiguous()
-    if batch_first:
-        (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
-    else:
-        (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
     if targets.shape[0] != B:
         raise ValueError(f"ctc_align: targets has {targets.shape[0]} rows for a batch of {B}")
     dev = lp.device
-    Lmax = targets.shape[1]
-    tg = targets.to(device=dev, dtype=torch.long, non_blocking=True)
-    if Lmax == 0:
-        tg = torch.zeros((B, 1), dtype=torch.long, device=dev)
-    elif tg.stride(1) != 1 or tg.stride(0) < Lmax:
-        tg = tg.contiguous()
-    il = _ctc_lengths(input_lengths, "input_lengths", B, dev)
-    tl = _ctc_lengths(target_lengths, "target_lengths", B, dev)
+    tg, Lmax = _ctc_targets(targets, B, dev)
+    il = _ctc_lengths("ctc_align", "input_lengths", input_lengths, B, dev)
+    tl = _ctc_lengths("ctc_align", "target_lengths", target_lengths, B, dev)
     S_max = 2 * Lmax + 1
     states = torch.empty((B, T), dtype=torch.int32, device=dev)
     spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
@@ -791,44 +785,12 @@ def _conf_codes(who: str, method=None, alpha=None, aggregation=None):
     return m, alpha, a
 
 
-def _conf_rows(who: str, log_probs, batch_first: bool):
-    """The validated [B, T, V] / [T, B, V] block of a confidence call -> (view with contiguous rows, B, T, V, stride_b, stride_t)."""
-    if not isinstance(log_probs, Tensor) or not log_probs.is_cuda:
-        raise RuntimeError(f"{who} (HIP): log_probs must be on the GPU; there is no CPU fallback (confidence.py runs host tensors)")
-    if log_probs.dim() != 3:
-        raise ValueError(f"{who}: log_probs must be [B, T, V] (or [T, B, V] with batch_first=False), got shape {tuple(log_probs.shape)}")
-    if log_probs.dtype != torch.float32:
-        raise TypeError(f"{who}: log_probs must be float32, got {log_probs.dtype}")
-    lp = log_probs.detach()
-    if lp.stride(2) != 1:
-        lp = lp.contiguous()
-    if batch_first:
-        (B, T, V), sb, st = lp.shape, lp.stride(0), lp.stride(1)
-    else:
-        (T, B, V), st, sb = lp.shape, lp.stride(0), lp.stride(1)
-    if V < 2 or not 1 <= T <= 4096:
-        raise ValueError(f"{who}: need V >= 2 and 1 <= T <= 4096, got T={T} V={V}")
-    return lp, B, T, V, sb, st
-
-
-def _conf_lengths(who: str, t, B: int, device) -> Optional[Tensor]:
-    if t is None:
-        return None
-    if not isinstance(t, Tensor):
-        t = torch.as_tensor(t, dtype=torch.long)
-    if t.dim() != 1 or t.numel() != B:
-        raise ValueError(f"{who}: lengths must hold one length per batch item ({B}), got shape {tuple(t.shape)}")
-    if t.dtype.is_floating_point or t.dtype == torch.bool:
-        raise TypeError(f"{who}: lengths must be an integer tensor, got {t.dtype}")
-    return t.to(device=device, dtype=torch.long, non_blocking=True).contiguous()
-
-
 def ctc_frame_conf(log_probs: Tensor, lengths=None, method: str = "tsallis", alpha: float = 0.33, batch_first: bool = True) -> Tensor:
     """av_ctc_frame_conf: ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]; any view with a contiguous last dimension is
     taken without a copy), ``lengths`` [B] on either side or None -> confidence fp32 [B, T] on the device, 0 for t >= T_b."""
     m, alpha, _ = _conf_codes("ctc_frame_conf", method, alpha)
-    lp, B, T, V, sb, st = _conf_rows("ctc_frame_conf", log_probs, batch_first)
-    ln = _conf_lengths("ctc_frame_conf", lengths, B, lp.device)
+    lp, B, T, V, sb, st = _ctc_rows("ctc_frame_conf", log_probs, batch_first, max_T=4096, min_V=2)
+    ln = _ctc_lengths("ctc_frame_conf", "lengths", lengths, B, lp.device, optional=True)
     conf = torch.empty((B, T), dtype=torch.float32, device=lp.device)
     L.check(L.lib().av_ctc_frame_conf(ptr(lp), sb, st, ptr(ln), B, T, V, m, alpha, ptr(conf), stream()), "av_ctc_frame_conf")
     return conf
@@ -854,7 +816,7 @@ def ctc_span_conf(frame_conf: Tensor, spans: Tensor, lengths=None, aggregation: 
     Ls = spans.shape[1]
     cf = frame_conf.detach().contiguous()
     sp = spans.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
-    ln = _conf_lengths("ctc_span_conf", lengths, B, dev)
+    ln = _ctc_lengths("ctc_span_conf", "lengths", lengths, B, dev, optional=True)
     out = torch.empty((B, Ls), dtype=torch.float32, device=dev)
     L.check(L.lib().av_ctc_span_conf(ptr(cf), ptr(sp), ptr(ln), B, T, Ls, a, ptr(out), stream()), "av_ctc_span_conf")
     return out
@@ -865,12 +827,12 @@ def ctc_greedy_timed(log_probs: Tensor, blank: int, lengths=None, method: str = 
     """av_ctc_greedy_timed: one read of ``log_probs`` (as for ``ctc_frame_conf``) -> (ids int32 [B, T] padded with -1, lengths int32 [B],
     spans int32 [B, T, 2] padded with -1, token_conf fp32 [B, T], frame_conf fp32 [B, T]) on the device."""
     m, alpha, a = _conf_codes("ctc_greedy_timed", method, alpha, aggregation)
-    lp, B, T, V, sb, st = _conf_rows("ctc_greedy_timed", log_probs, batch_first)
+    lp, B, T, V, sb, st = _ctc_rows("ctc_greedy_timed", log_probs, batch_first, max_T=4096, min_V=2)
     blank = int(blank)
     if not 0 <= blank < V:
         raise ValueError(f"ctc_greedy_timed: blank {blank} outside [0, {V})")
     dev = lp.device
-    ln = _conf_lengths("ctc_greedy_timed", lengths, B, dev)
+    ln = _ctc_lengths("ctc_greedy_timed", "lengths", lengths, B, dev, optional=True)
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     cnt = torch.empty((B,), dtype=torch.int32, device=dev)
     spans = torch.empty((B, T, 2), dtype=torch.int32, device=dev)
