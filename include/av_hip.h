@@ -485,6 +485,28 @@ int av_ctc_cut_points(const float* log_probs, long long stride_s, long long stri
                       int* cuts, void* stream);
 int av_ctc_segment_gather(const float* log_probs, long long stride_s, long long stride_t, const int* cuts, int S, int F, int V, int nb,
                           int segment, float* seg_log_probs, long long* seg_lengths, void* stream);
+/* CTC keyword spotting on the device (csrc/ctc_spot.hip; spot.py restates the law in float32 numpy, bit for bit): was this
+ * phrase said, where, and how sure - K keywords against every utterance of one block of log-probs.  fp32, no atomics, no synchronisation.
+ * log_probs and strides as for av_ctc_align ([B][T][V] and the [T][B][V] view are both taken without a copy); input_lengths int64 [B] in
+ * DEVICE memory or NULL (= T), clamped to [0, T]; there is no limit on T other than memory.  keywords int32 [K][kw_ld] and kw_lengths
+ * int32 [K] in DEVICE memory: keyword k is its first L_k = kw_lengths[k] clamped to [0, L_max] ids; it is INVALID - no hits - if
+ * L_k < 1, if an id is outside [0, V) or if an id equals the blank.  1 <= L_max <= 32 (one lattice state per lane), kw_ld >= L_max.
+ * The law: m[t] = max_v lp[t][v] (a NaN never wins), c[t][v] = lp[t][v] - m[t] (every cost of a frame whose m is not finite is -inf).
+ * Lattice of S = 2 L - 1 states y_1, blank, y_2, ..., blank, y_L; the skip s-2 -> s exists for even s >= 2 with y differing from the
+ * label two states back.  Each cell carries (d, start), (-inf, -1) before frame 0; at frame t state s takes d[t-1][s], then
+ * d[t-1][s-1] if strictly greater, then the skip predecessor if it exists and is strictly greater, and state 0 alone a fresh start
+ * (0, t) if 0 is strictly greater; d[t][s] = best + c[t][label_s].  e[t] = d[t][S-1], es[t] = start[t][S-1].  Hits: among the frames
+ * t < T_b with e[t] > -inf and e[t] >= min_score, up to N times the greatest e[t] (ties: the greater t) is reported as
+ * (es[t], t + 1, e[t]) and every frame u whose interval [es[u], u + 1) overlaps it is dropped.  A score is the log-likelihood ratio of
+ * the path against the best unconstrained path over the same frames: <= 0, and 0.0 exactly on an argmax path.
+ * out_hits int32 [B][K][N][2] (first frame, end frame exclusive; -1 padded), out_scores fp32 [B][K][N] (descending; -inf padded),
+ * out_counts int32 [B][K].  1 <= N <= 8; min_score may be -inf, not NaN.
+ * workspace: av_ctc_spot_workspace_bytes(B, T, K) = 4 B T (1 + 2 K) bytes (m [B][T], then e fp32 and es int32 [B][K][T]), 4-byte
+ * aligned; a smaller one is an error status. */
+int av_ctc_spot_workspace_bytes(int B, int T, int K, long long* bytes);
+int av_ctc_spot(const float* log_probs, long long stride_b, long long stride_t, const long long* input_lengths, const int* keywords,
+                long long kw_ld, const int* kw_lengths, int B, int T, int V, int K, int L_max, int blank, int N, float min_score,
+                int* out_hits, float* out_scores, int* out_counts, void* workspace, long long workspace_bytes, void* stream);
 /* Word, character and token error counts on the device: edit distance with operation counts between ONE reference and N hypotheses per
  * utterance, from token ids through a device copy of the tokenizer's piece table - what MultimodalTrainer.evaluate() measures
  * (word_error_rate of model/trainer.py, the jiwer.wer stand-in), plus the character and token levels and the S / D / I breakdown.

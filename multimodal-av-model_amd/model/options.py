@@ -70,6 +70,10 @@ OPTIONS = {
     "long_batch": ("AVAMD_LONG_BATCH", int, "16", int),
     "long_segment": ("AVAMD_LONG_SEGMENT", int, "400", int),
     "long_radius": ("AVAMD_LONG_RADIUS", int, "50", int),
+    # spot() and spot_long() (spot.py), read by them alone where the call gives None: the lowest score a hit may have (a log-likelihood ratio,
+    # <= 0; "-inf" keeps every hit) and the hits reported per utterance and keyword (1 .. 8)
+    "spot_min_score": ("AVAMD_SPOT_MIN_SCORE", float, "-inf", float),
+    "spot_max_hits": ("AVAMD_SPOT_MAX_HITS", int, "4", int),
 }
 
 
@@ -110,6 +114,14 @@ def check_longform(window: int, stride: int, policy: str, batch: int, segment: i
                          f"{min_average_hop(window)}, long_window - 2 long_stride is {hop}")
     if batch < 1:
         raise ValueError(f"long_batch must be >= 1, got {batch}")
+
+
+def check_spot(min_score: float, max_hits: int) -> None:
+    from ..spot import MAX_HITS
+    if min_score != min_score:
+        raise ValueError("spot_min_score must not be NaN")
+    if not 1 <= max_hits <= MAX_HITS:
+        raise ValueError(f"spot_max_hits must be in [1, {MAX_HITS}], got {max_hits}")
 
 
 def check_ema(eval_ema: bool, ema_decay: float) -> None:

@@ -74,7 +74,8 @@ class MultimodalTrainer:
                  conf_alpha: Optional[float] = None, conf_aggregation: Optional[str] = None, weight_decay: Optional[float] = None,
                  lr_schedule: Optional[str] = None, accum_steps: Optional[int] = None, long_window: Optional[int] = None,
                  long_stride: Optional[int] = None, long_policy: Optional[str] = None, long_batch: Optional[int] = None,
-                 long_segment: Optional[int] = None, long_radius: Optional[int] = None):
+                 long_segment: Optional[int] = None, long_radius: Optional[int] = None, spot_min_score: Optional[float] = None,
+                 spot_max_hits: Optional[int] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -101,6 +102,8 @@ class MultimodalTrainer:
         self.long_policy, self.long_batch = opt("long_policy", long_policy), opt("long_batch", long_batch)
         self.long_segment, self.long_radius = opt("long_segment", long_segment), opt("long_radius", long_radius)
         options.check_longform(self.long_window, self.long_stride, self.long_policy, self.long_batch, self.long_segment, self.long_radius)
+        self.spot_min_score, self.spot_max_hits = opt("spot_min_score", spot_min_score), opt("spot_max_hits", spot_max_hits)
+        options.check_spot(self.spot_min_score, self.spot_max_hits)
         self.mwer_weight, self.mwer_nbest = opt("mwer_weight", mwer_weight), opt("mwer_nbest", mwer_nbest)
         self.mwer_beam, self.mwer_level = opt("mwer_beam", mwer_beam), mwer_level
         options.check_mwer(self.mwer_weight, self.mwer_nbest, self.mwer_beam, mwer_level)
@@ -748,31 +751,8 @@ class MultimodalTrainer:
         F_, seg, rad = lip1.shape[0], self.long_segment, self.long_radius
         plan = longform.plan_windows(F_, self.long_window, self.long_stride)
         plan.sources(self.long_policy)                             # a plan the policy cannot join raises before anything runs
-        Wd, nw, buf = plan.width, plan.count, None
         with self._inference():
-            mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
-            modes = [(sm, sm.training) for m in mods for sm in m.modules()]
-            for m in mods:
-                m.eval()
-            try:
-                for k0 in range(0, nw, self.long_batch):
-                    ks = range(k0, min(k0 + self.long_batch, nw))
-                    out = self.forward_log_probs({
-                        "audio": torch.stack([audio[slice(*plan.audio_window(k))] for k in ks]),
-                        "lip1": torch.stack([lip1[plan.starts[k]:plan.starts[k] + Wd] for k in ks]),
-                        "lip2": torch.stack([lip2[plan.starts[k]:plan.starts[k] + Wd] for k in ks])})
-                    self.fusion_module.stage_flag_check()
-                    for s, spk in enumerate(("1", "2")):
-                        lp = out["log_probs" + spk]
-                        if lp.shape[1] != Wd:
-                            raise RuntimeError(f"transcribe_long: a window of {Wd} lip frames came back with {lp.shape[1]} CTC frames")
-                        if buf is None:
-                            buf = torch.empty((2, nw, Wd, lp.shape[2]), dtype=torch.float32, device=lp.device)
-                        buf[s, k0:k0 + len(ks)].copy_(lp)
-            finally:
-                for sm, was in modes:
-                    sm.training = was
-            stitched = longform.stitch(buf, plan, self.long_policy)
+            stitched = self._stitched_windows("transcribe_long", plan, audio, lip1, lip2)
             if F_ <= seg:                                          # one segment per speaker: exactly what transcribe() decodes
                 cuts = ops.h2d_async(torch.tensor([[0, F_]] * 2, dtype=torch.int32).numpy(), stitched.device)
                 flat, T = self._transcribe_device(stitched, nbest), F_
@@ -806,6 +786,108 @@ class MultimodalTrainer:
                         "words": word_segments(self.tokenizer, ids, spans, ts, frame_rate, token_conf=tc, aggregation=self.conf_aggregation),
                         "segments": parts})
         return tuple(res)
+
+    def _stitched_windows(self, who, plan, audio, lip1, lip2):
+        """What transcribe_long() and spot_long() share, inside ``_inference()``: the plan's windows through forward_log_probs ``long_batch``
+        at a time in eval mode (every module's train / eval mode restored) into one [2, nw, W, V] device buffer, stitched by ``long_policy``
+        -> float32 [2, F, V] on the device."""
+        from .. import longform
+        Wd, nw, buf = plan.width, plan.count, None
+        mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+        modes = [(sm, sm.training) for m in mods for sm in m.modules()]
+        for m in mods:
+            m.eval()
+        try:
+            for k0 in range(0, nw, self.long_batch):
+                ks = range(k0, min(k0 + self.long_batch, nw))
+                out = self.forward_log_probs({
+                    "audio": torch.stack([audio[slice(*plan.audio_window(k))] for k in ks]),
+                    "lip1": torch.stack([lip1[plan.starts[k]:plan.starts[k] + Wd] for k in ks]),
+                    "lip2": torch.stack([lip2[plan.starts[k]:plan.starts[k] + Wd] for k in ks])})
+                self.fusion_module.stage_flag_check()
+                for s, spk in enumerate(("1", "2")):
+                    lp = out["log_probs" + spk]
+                    if lp.shape[1] != Wd:
+                        raise RuntimeError(f"{who}: a window of {Wd} lip frames came back with {lp.shape[1]} CTC frames")
+                    if buf is None:
+                        buf = torch.empty((2, nw, Wd, lp.shape[2]), dtype=torch.float32, device=lp.device)
+                    buf[s, k0:k0 + len(ks)].copy_(lp)
+        finally:
+            for sm, was in modes:
+                sm.training = was
+        return longform.stitch(buf, plan, self.long_policy)
+
+    # ---- keyword spotting: was this phrase said, where, and how sure (spot.py, csrc/ctc_spot.hip) ----
+    def _spot_keywords(self, who, keywords, max_hits, min_score):
+        """-> (ContextBias, the keywords' names, max_hits, min_score): strings go through ``ContextBias.from_phrases`` with the tokenizer, one
+        string or path is a phrase file, a ContextBias is taken as it is; None reads ``spot_max_hits`` / ``spot_min_score``."""
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError(f"MultimodalTrainer.{who}: the model runs on the GPU; there is no CPU fallback")
+        if isinstance(keywords, (str, os.PathLike)):
+            keywords = ContextBias.from_file(keywords, self.tokenizer)
+        elif not isinstance(keywords, ContextBias):
+            keywords = ContextBias.from_phrases(list(keywords), self.tokenizer)
+        if not keywords.phrases:
+            raise ValueError(f"{who}: no keywords")
+        max_hits = self.spot_max_hits if max_hits is None else int(max_hits)
+        min_score = self.spot_min_score if min_score is None else float(min_score)
+        options.check_spot(min_score, max_hits)
+        pieces = self.tokenizer.id_to_token
+        names = ["".join(pieces[i] for i in p).replace("▁", " ") for p in keywords.phrases]
+        return keywords, names, max_hits, min_score
+
+    def _spot_device(self, lp, bias, max_hits, min_score):
+        """One block of log-probs [B, T, V] -> flat int32 block on the device: per (utterance, keyword) ``max_hits`` rows of (first frame, end
+        frame, bits of the score), then the counts."""
+        from ..spot import keyword_spot
+        s = keyword_spot(lp, bias, blank=self.tokenizer.blank_id, max_hits=max_hits, min_score=min_score)
+        return torch.cat([torch.cat([s.hits, s.scores.view(torch.int32)[..., None]], 3).reshape(-1), s.counts.reshape(-1)])
+
+    @staticmethod
+    def _spot_host(flat, B, K, N, names, frame_rate):
+        from ..spot import Spots, hit_segments
+        main = flat[:B * K * N * 3].view(B, K, N, 3)
+        return hit_segments(Spots(main[..., :2], main[..., 2].contiguous().view(torch.float32), flat[B * K * N * 3:].view(B, K)), names, frame_rate)
+
+    def spot(self, batch, keywords, max_hits: Optional[int] = None, min_score: Optional[float] = None, frame_rate: float = 25.0):
+        """Where both speakers of a batch said the ``keywords``: strings (``ContextBias.from_phrases`` with the tokenizer), the path of a phrase
+        file, or a ``ContextBias``.  The batch needs no ``text*`` and no ``mask*`` keys (forward_log_probs); eval mode and ``eval_ema`` as
+        in transcribe().  ``max_hits`` hits per utterance and keyword (None: ``spot_max_hits``) with a score of at least ``min_score``
+        (None: ``spot_min_score``) - spot.keyword_spot over all T frames.  Returns (hits1, hits2): per utterance the ``spot.hit_segments``
+        list (keyword, start, end, score, per_frame).  Nothing travels to the host before the end; then ONE int32 block per speaker.
+        Every module's train / eval mode is restored; a timed-out persistent BiLSTM launch raises here as it does from evaluate()."""
+        bias, names, N, ms = self._spot_keywords("spot", keywords, max_hits, min_score)
+        with self._inference():
+            mods = (self.visual_encoder, self.audio_encoder, self.fusion_module, self.decoder1)
+            modes = [(sm, sm.training) for m in mods for sm in m.modules()]
+            for m in mods:
+                m.eval()
+            try:
+                out = self.forward_log_probs(batch)
+            finally:
+                for sm, was in modes:
+                    sm.training = was
+            self.fusion_module.stage_flag_check()
+            B = out["log_probs1"].shape[0]
+            packed = [self._spot_device(out["log_probs" + spk].float(), bias, N, ms) for spk in ("1", "2")]
+            host = [p.cpu() for p in packed]                       # the only transfers: one int32 block per speaker
+            self.fusion_module.drain_flag_check()                  # raises if a persistent BiLSTM launch timed out
+        return tuple(self._spot_host(h, B, len(names), N, names, frame_rate) for h in host)
+
+    def spot_long(self, recording, keywords, max_hits: Optional[int] = None, min_score: Optional[float] = None, frame_rate: float = 25.0):
+        """spot() for ONE recording of any length (``recording`` as for transcribe_long): its windows and stitch, then spot.keyword_spot on
+        the stitched [2, F, V] - there is no bound on F other than memory, and a hit may lie across any window edge.  Returns (hits1,
+        hits2): per speaker the ``spot.hit_segments`` list, times counted from the start of the recording.  ONE transfer at the end."""
+        from .. import longform
+        bias, names, N, ms = self._spot_keywords("spot_long", keywords, max_hits, min_score)
+        audio, lip1, lip2 = self._recording(recording)
+        plan = longform.plan_windows(lip1.shape[0], self.long_window, self.long_stride)
+        plan.sources(self.long_policy)                             # a plan the policy cannot join raises before anything runs
+        with self._inference():
+            stitched = self._stitched_windows("spot_long", plan, audio, lip1, lip2)
+            host = self._spot_device(stitched, bias, N, ms).cpu()  # the only transfer
+            self.fusion_module.drain_flag_check()
+        return tuple(self._spot_host(host, 2, len(names), N, names, frame_rate))
 
     @staticmethod
     def _recording(recording):

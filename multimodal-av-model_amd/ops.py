@@ -762,6 +762,41 @@ def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths,
     return states, spans, tok, score
 
 
+def ctc_spot(log_probs: Tensor, keywords: Tensor, kw_lengths, input_lengths=None, blank: int = 0, max_hits: int = 4,
+             min_score: float = float("-inf"), batch_first: bool = True):
+    """CTC keyword spotting on the kernels of csrc/ctc_spot.hip: ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]; any view
+    with a contiguous last dimension is taken without a copy, T has no limit), ``keywords`` integer [K, Lmax <= 32] padded, ``kw_lengths``
+    [K] and ``input_lengths`` [B] or None on the device (nothing is read back) or on the host (copied without blocking).  Returns (hits
+    int32 [B, K, max_hits, 2] padded with -1, scores fp32 [B, K, max_hits] padded with -inf, counts int32 [B, K]) on the device; the
+    law: spot.py."""
+    lp, B, T, V, sb, st = _ctc_rows("ctc_spot", log_probs, batch_first)
+    if not isinstance(keywords, Tensor) or keywords.dim() != 2 or keywords.dtype.is_floating_point or keywords.dtype == torch.bool:
+        raise TypeError("ctc_spot: keywords must be an integer tensor [K, Lmax], got "
+                        f"{(keywords.dtype, tuple(keywords.shape)) if isinstance(keywords, Tensor) else type(keywords).__name__}")
+    K, Lmax = keywords.shape
+    N, blank, min_score = int(max_hits), int(blank), float(min_score)
+    if not 1 <= Lmax <= 32 or not 1 <= N <= 8 or min_score != min_score or not 0 <= blank < V:
+        raise ValueError(f"ctc_spot: need 1 <= Lmax <= 32, 1 <= max_hits <= 8, 0 <= blank < V and a min_score that is not NaN, got Lmax={Lmax} "
+                         f"max_hits={N} blank={blank} V={V} min_score={min_score}")
+    dev = lp.device
+    hits = torch.empty((B, K, N, 2), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K, N), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, K), dtype=torch.int32, device=dev)
+    if B == 0 or K == 0:
+        return hits, scores, counts
+    kw = keywords.to(device=dev, dtype=torch.int32, non_blocking=True)
+    if kw.stride(1) != 1 or kw.stride(0) < Lmax:
+        kw = kw.contiguous()
+    kl = _ctc_lengths("ctc_spot", "kw_lengths", kw_lengths, K, dev).to(torch.int32)
+    il = _ctc_lengths("ctc_spot", "input_lengths", input_lengths, B, dev, optional=True)
+    need = L.ll(0)
+    L.check(L.lib().av_ctc_spot_workspace_bytes(B, T, K, C.byref(need)), "av_ctc_spot_workspace_bytes")
+    ws = torch.empty((need.value // 4,), dtype=torch.int32, device=dev)
+    L.check(L.lib().av_ctc_spot(ptr(lp), sb, st, ptr(il), ptr(kw), kw.stride(0), ptr(kl), B, T, V, K, Lmax, blank, N, min_score, ptr(hits),
+                                ptr(scores), ptr(counts), ptr(ws), ws.numel() * 4, stream()), "av_ctc_spot")
+    return hits, scores, counts
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # CTC confidences on the device (csrc/ctc_confidence.hip; the laws and the host path: confidence.py).  Lengths and spans stay on the
 # device, nothing in a call synchronises.
