@@ -507,6 +507,27 @@ int av_ctc_spot_workspace_bytes(int B, int T, int K, long long* bytes);
 int av_ctc_spot(const float* log_probs, long long stride_b, long long stride_t, const long long* input_lengths, const int* keywords,
                 long long kw_ld, const int* kw_lengths, int B, int T, int V, int K, int L_max, int blank, int N, float min_score,
                 int* out_hits, float* out_scores, int* out_counts, void* workspace, long long workspace_bytes, void* stream);
+/* CTC segmentation on the device (csrc/ctc_segment.hip; segmentation.py holds the law in full and restates it in float32 numpy, bit for
+ * bit): a known transcript laid over a recording of any length - av_ctc_align without its limits, with ends that may float, a
+ * score per frame and a confidence per utterance.  fp32, no atomics, no synchronisation.  log_probs, strides, targets, target_ld and the
+ * two length arrays as for av_ctc_align; there is no limit on T other than memory, S_max = 2 Lmax + 1 <= 16383 (Lmax 8191), V <= 12000
+ * (whole rows of log-probs are staged in LDS).  free_ends: bit 0 = the path may start at any frame, bit 1 = it may end at any frame;
+ * with free_ends = 0 out_state, out_span, out_token_score and out_score are bit for bit av_ctc_align's, otherwise emissions are
+ * lp[t][c] - max_v lp[t][v] and the score is a log-likelihood ratio against the best unconstrained path over the same frames.
+ * utterances int32 [B][U][2] in DEVICE memory: token ranges [begin, end) into the target, used only if 0 <= begin < end <= L_b; U may
+ * be 0 (then utterances and the three out_utt_* may be NULL).  score_window >= 1: frames per window of out_utt_score.
+ * out_state int32 [B][T] (-1 off the path), out_span int32 [B][Lmax][2], out_token_score fp32 [B][Lmax], out_score fp32 [B] (-inf:
+ * infeasible), out_frame_score fp32 [B][T] (the path's emission per frame, 0 off the path), out_utt_span int32 [B][U][2] (first frame
+ * of token begin, end frame of token end-1; -1, -1 where there is none), out_utt_mean fp32 [B][U] (mean frame score over the span),
+ * out_utt_score fp32 [B][U] (the least mean over its consecutive windows of score_window frames).
+ * workspace: av_ctc_segment_workspace_bytes(B, T, S_max) = 4 B ceil(T / 16) S_max bytes (2 bits per frame and state), 4-byte aligned; a
+ * smaller one is an error status. */
+int av_ctc_segment_workspace_bytes(int B, int T, int S_max, long long* bytes);
+int av_ctc_segment(const float* log_probs, long long stride_b, long long stride_t, const long long* targets, long long target_ld,
+                   const long long* input_lengths, const long long* target_lengths, const int* utterances, int B, int T, int V, int S_max,
+                   int U, int blank, int free_ends, int score_window, int* out_state, int* out_span, float* out_token_score,
+                   float* out_score, float* out_frame_score, int* out_utt_span, float* out_utt_mean, float* out_utt_score, void* workspace,
+                   long long workspace_bytes, void* stream);
 /* Word, character and token error counts on the device: edit distance with operation counts between ONE reference and N hypotheses per
  * utterance, from token ids through a device copy of the tokenizer's piece table - what MultimodalTrainer.evaluate() measures
  * (word_error_rate of model/trainer.py, the jiwer.wer stand-in), plus the character and token levels and the S / D / I breakdown.

@@ -171,6 +171,8 @@ SIGNATURES = {
     "av_ctc_segment_gather": [vp, ll, ll, vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "av_ctc_spot_workspace_bytes": [i32, i32, i32, C.POINTER(ll)],
     "av_ctc_spot": [vp, ll, ll, vp, vp, ll, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, ll, vp],
+    "av_ctc_segment_workspace_bytes": [i32, i32, i32, C.POINTER(ll)],
+    "av_ctc_segment": [vp, ll, ll, vp, ll, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, vp],
     "av_error_counts_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(ll)],
     "av_error_counts": [vp, ll, vp, vp, ll, ll, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, ll, vp],
     "av_augment_lips": [vp, vp, vp, i32, i32, i32, i32, C.c_ulonglong, ll, C.c_uint, i32, i32, i32, i32, vp],

@@ -74,6 +74,10 @@ OPTIONS = {
     # <= 0; "-inf" keeps every hit) and the hits reported per utterance and keyword (1 .. 8)
     "spot_min_score": ("AVAMD_SPOT_MIN_SCORE", float, "-inf", float),
     "spot_max_hits": ("AVAMD_SPOT_MAX_HITS", int, "4", int),
+    # align_long() (segmentation.py), read by it alone where the call gives None: the frames per window of an utterance's score (the least
+    # window mean) and which ends of the path may float - 0 none, 1 the start, 2 the end, 3 both
+    "segment_window": ("AVAMD_SEGMENT_WINDOW", int, "30", int),
+    "segment_free": ("AVAMD_SEGMENT_FREE", int, "0", int),
 }
 
 
@@ -122,6 +126,13 @@ def check_spot(min_score: float, max_hits: int) -> None:
         raise ValueError("spot_min_score must not be NaN")
     if not 1 <= max_hits <= MAX_HITS:
         raise ValueError(f"spot_max_hits must be in [1, {MAX_HITS}], got {max_hits}")
+
+
+def check_segmentation(window: int, free: int) -> None:
+    if window < 1:
+        raise ValueError(f"segment_window must be >= 1, got {window}")
+    if not 0 <= free <= 3:
+        raise ValueError(f"segment_free must be 0 (fixed ends), 1 (free start), 2 (free end) or 3 (both), got {free}")
 
 
 def check_ema(eval_ema: bool, ema_decay: float) -> None:

@@ -75,7 +75,7 @@ class MultimodalTrainer:
                  lr_schedule: Optional[str] = None, accum_steps: Optional[int] = None, long_window: Optional[int] = None,
                  long_stride: Optional[int] = None, long_policy: Optional[str] = None, long_batch: Optional[int] = None,
                  long_segment: Optional[int] = None, long_radius: Optional[int] = None, spot_min_score: Optional[float] = None,
-                 spot_max_hits: Optional[int] = None):
+                 spot_max_hits: Optional[int] = None, segment_window: Optional[int] = None, segment_free: Optional[int] = None):
         """The opt-in settings (a None argument reads its AVAMD_* variable here) are the rows of model/options.py."""
         self.visual_encoder = visual_encoder.to(device)
         self.audio_encoder = audio_encoder.to(device)
@@ -104,6 +104,8 @@ class MultimodalTrainer:
         options.check_longform(self.long_window, self.long_stride, self.long_policy, self.long_batch, self.long_segment, self.long_radius)
         self.spot_min_score, self.spot_max_hits = opt("spot_min_score", spot_min_score), opt("spot_max_hits", spot_max_hits)
         options.check_spot(self.spot_min_score, self.spot_max_hits)
+        self.segment_window, self.segment_free = opt("segment_window", segment_window), opt("segment_free", segment_free)
+        options.check_segmentation(self.segment_window, self.segment_free)
         self.mwer_weight, self.mwer_nbest = opt("mwer_weight", mwer_weight), opt("mwer_nbest", mwer_nbest)
         self.mwer_beam, self.mwer_level = opt("mwer_beam", mwer_beam), mwer_level
         options.check_mwer(self.mwer_weight, self.mwer_nbest, self.mwer_beam, mwer_level)
@@ -888,6 +890,71 @@ class MultimodalTrainer:
             host = self._spot_device(stitched, bias, N, ms).cpu()  # the only transfer
             self.fusion_module.drain_flag_check()
         return tuple(self._spot_host(host, 2, len(names), N, names, frame_rate))
+
+    # ---- a recording against its transcript: word and utterance times with scores (segmentation.py, csrc/ctc_segment.hip) ----
+    def _segment_targets(self, transcripts):
+        """Two transcripts (a string = one utterance, or a list of strings) -> (per speaker the token ids, targets int64 [2, Lmax] padded
+        with the blank, their lengths, utterances int32 [2, U, 2] padded with -1, per speaker the utterances' texts).  Every utterance goes
+        through ``tokenizer.encode``; a '▁' piece is put between two utterances where the tokenizer has one - it belongs to neither."""
+        space = self.tokenizer.token_to_id.get("▁")
+        texts = [[t] if isinstance(t, str) else [str(x) for x in t] for t in transcripts]
+        ids, ranges = [], []
+        for utts in texts:
+            row, rng = [], []
+            for k, text in enumerate(utts):
+                if k and space is not None:
+                    row.append(int(space))
+                rng.append((len(row), len(row) + len(enc := [int(i) for i in self.tokenizer.encode(text)])))
+                row += enc
+            ids.append(row)
+            ranges.append(rng)
+        Lmax, U = max(len(r) for r in ids), max(len(r) for r in ranges)
+        tg = torch.full((2, Lmax), int(self.tokenizer.blank_id), dtype=torch.long)
+        ut = torch.full((2, U, 2), -1, dtype=torch.int32)
+        for i in range(2):
+            tg[i, :len(ids[i])] = torch.tensor(ids[i], dtype=torch.long)
+            if ranges[i]:
+                ut[i, :len(ranges[i])] = torch.tensor(ranges[i], dtype=torch.int32)
+        return ids, tg, torch.tensor([len(r) for r in ids]), ut, texts
+
+    def align_long(self, recording, transcript1, transcript2, frame_rate: float = 25.0, free_start: Optional[bool] = None,
+                   free_end: Optional[bool] = None):
+        """Where in ONE recording of any length (``recording`` as for transcribe_long) each speaker's transcript was said: a transcript is
+        a string (one utterance) or a list of strings (utterances, joined by a '▁' piece where the tokenizer has one).  The windows
+        and the stitch of transcribe_long, then segmentation.ctc_segment on the stitched [2, F, V]: no bound on F other than memory, up to
+        8191 tokens per transcript.  ``free_start`` / ``free_end`` (None: bits 0 / 1 of ``segment_free``) let the transcript begin after
+        and end before the recording does; utterance scores use windows of ``segment_window`` frames.  Returns (result1, result2), a dict
+        per speaker: ``score`` (the path's; -inf with empty lists for a transcript that cannot be aligned), ``words``
+        (``align.word_segments``, times counted from the start of the recording) and ``utterances``
+        (``segmentation.utterance_segments``: text, start, end, score, mean).  ONE int32 block goes to the host at the end."""
+        from .. import longform
+        from ..segmentation import Segmentation, ctc_segment, utterance_segments
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("MultimodalTrainer.align_long: the model runs on the GPU; there is no CPU fallback")
+        fs = bool(self.segment_free & 1) if free_start is None else bool(free_start)
+        fe = bool(self.segment_free & 2) if free_end is None else bool(free_end)
+        ids, tg, tl, ut, texts = self._segment_targets((transcript1, transcript2))
+        audio, lip1, lip2 = self._recording(recording)
+        plan = longform.plan_windows(lip1.shape[0], self.long_window, self.long_stride)
+        plan.sources(self.long_policy)                             # a plan the policy cannot join raises before anything runs
+        with self._inference():
+            stitched = self._stitched_windows("align_long", plan, audio, lip1, lip2)
+            dev = stitched.device                                  # targets, lengths and ranges: pinned copies that do not drain the stream
+            seg = ctc_segment(stitched, ops.h2d_async(tg.numpy(), dev), None, ops.h2d_async(tl.numpy(), dev), blank=self.tokenizer.blank_id,
+                              utterances=ops.h2d_async(ut.numpy(), dev), free_start=fs, free_end=fe, score_window=self.segment_window)
+            parts = [seg.spans, seg.token_scores.view(torch.int32), seg.score.view(torch.int32), seg.utt_spans,
+                     seg.utt_means.view(torch.int32), seg.utt_scores.view(torch.int32)]
+            host = torch.cat([x.reshape(-1) for x in parts]).cpu()  # the only transfer
+            self.fusion_module.drain_flag_check()
+        got, at = [], 0
+        for x in parts:
+            got.append(host[at:at + x.numel()].view(x.shape))
+            at += x.numel()
+        spans, tok, score, usp, um, us = (x if k in (0, 3) else x.contiguous().view(torch.float32) for k, x in enumerate(got))
+        utts = utterance_segments(Segmentation(None, spans, tok, score, None, usp, um, us), texts, frame_rate)
+        return tuple({"score": float(score[i]),
+                      "words": word_segments(self.tokenizer, ids[i], spans[i], tok[i], frame_rate) if bool(score[i] > float("-inf")) else [],
+                      "utterances": utts[i]} for i in range(2))
 
     @staticmethod
     def _recording(recording):

@@ -762,6 +762,54 @@ def ctc_align(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths,
     return states, spans, tok, score
 
 
+def ctc_segment(log_probs: Tensor, targets: Tensor, input_lengths, target_lengths, utterances=None, blank: int = 0, free: int = 0,
+                score_window: int = 30, batch_first: bool = True, max_workspace_bytes: int = 4 << 30):
+    """CTC segmentation on the kernel of csrc/ctc_segment.hip: ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]; any view with
+    a contiguous last dimension is taken without a copy, T has no limit), ``targets`` integer [B, Lmax <= 8191] padded, ``utterances``
+    integer [B, U, 2] token ranges or None; lengths, targets and utterances on the device (nothing is read back) or on the host (copied
+    without blocking).  ``free``: bit 0 = free start, bit 1 = free end.  Returns (states int32 [B, T], spans int32 [B, Lmax, 2],
+    token_scores fp32 [B, Lmax], score fp32 [B], frame_scores fp32 [B, T], utt_spans int32 [B, U, 2], utt_means fp32 [B, U], utt_scores
+    fp32 [B, U]) on the device; the law: segmentation.py.  The workspace this call owns holds 2 bits per frame and state; a shape that
+    needs more than ``max_workspace_bytes`` raises before anything is allocated."""
+    lp, B, T, V, sb, st = _ctc_rows("ctc_segment", log_probs, batch_first)
+    if targets.dim() != 2 or targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise TypeError(f"ctc_segment: targets must be an integer tensor [B, Lmax], got {targets.dtype} {tuple(targets.shape)}")
+    if targets.shape[0] != B:
+        raise ValueError(f"ctc_segment: targets has {targets.shape[0]} rows for a batch of {B}")
+    dev = lp.device
+    U = 0 if utterances is None else utterances.shape[1]
+    if utterances is not None and (utterances.dim() != 3 or utterances.shape[0] != B or utterances.shape[2] != 2
+                                   or utterances.dtype.is_floating_point or utterances.dtype == torch.bool):
+        raise TypeError(f"ctc_segment: utterances must be an integer tensor [B={B}, U, 2], got {utterances.dtype} {tuple(utterances.shape)}")
+    tg, Lmax = _ctc_targets(targets, B, dev)
+    il = _ctc_lengths("ctc_segment", "input_lengths", input_lengths, B, dev)
+    tl = _ctc_lengths("ctc_segment", "target_lengths", target_lengths, B, dev)
+    S_max = 2 * Lmax + 1
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    tok = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    frame = torch.empty((B, T), dtype=torch.float32, device=dev)
+    usp = torch.empty((B, U, 2), dtype=torch.int32, device=dev)
+    umean = torch.empty((B, U), dtype=torch.float32, device=dev)
+    uscore = torch.empty((B, U), dtype=torch.float32, device=dev)
+    if B == 0:
+        return states, spans, tok, score, frame, usp, umean, uscore
+    need = L.ll(0)
+    L.check(L.lib().av_ctc_segment_workspace_bytes(B, T, S_max, C.byref(need)), "av_ctc_segment_workspace_bytes")
+    if need.value > int(max_workspace_bytes):
+        raise ValueError(f"ctc_segment: T = {T} frames against L = {Lmax} labels (B = {B}) needs a move workspace of {need.value} bytes, more "
+                         f"than max_workspace_bytes = {int(max_workspace_bytes)}: split the recording or raise the limit")
+    ut = utterances.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous() if U else None
+    ws = torch.empty((max(1, (need.value + 3) // 4),), dtype=torch.int32, device=dev)
+    L.check(L.lib().av_ctc_segment(ptr(lp), sb, st, ptr(tg), tg.stride(0), ptr(il), ptr(tl), ptr(ut) if U else None, B, T, V, S_max, U,
+                                   int(blank), int(free), int(score_window), ptr(states), ptr(spans) if Lmax else None,
+                                   ptr(tok) if Lmax else None, ptr(score), ptr(frame), ptr(usp) if U else None,
+                                   ptr(umean) if U else None, ptr(uscore) if U else None, ptr(ws), ws.numel() * 4, stream()),
+            "av_ctc_segment")
+    return states, spans, tok, score, frame, usp, umean, uscore
+
+
 def ctc_spot(log_probs: Tensor, keywords: Tensor, kw_lengths, input_lengths=None, blank: int = 0, max_hits: int = 4,
              min_score: float = float("-inf"), batch_first: bool = True):
     """CTC keyword spotting on the kernels of csrc/ctc_spot.hip: ``log_probs`` fp32 [B, T, V] (``batch_first=False``: [T, B, V]; any view
